@@ -19,7 +19,14 @@ GPU, 9 octaves x 60 bins/octave; weak scaling (per-GPU batch fixed).  The step r
 (experiments/train.py:415): dtype = bf16 (bf16 channels-last MFMA conv path, fp32 master weights / losses / optimizer);
 `--precision fp32` times the exact-fp32 path that carries the 1e-4 output bar (also reported as "fp32_train_step").
 
-Prints ONE JSON line on rank 0 with the driver's fields plus
+A plain run sets up, warms up, times the --steps steps and prints ONE JSON line on rank 0 with the driver's fields (metric, value,
+unit, higher_is_better, dtype, ms_per_step, ...), the peak memory, the per-rank step times and the loss of the last timed step.
+`--dump-outputs DIR` then also writes what the last timed step computed as DIR/<name>.npy (float32; once the arrays exceed 60 MB
+in all -- DUMP_LIMIT_BYTES, which keeps the files under 64 MB -- a fixed seeded sample of each array larger than its share): the
+train step's loss terms, the updated flat parameters and the flat gradient; `--mode infer`: the activations and the reconstructed audio.  Inputs and initial weights are seeded, so two builds given the same
+arguments can be compared output for output.
+
+`--full` adds, after the timed steps, every other figure below (on rank 0 of the line):
   "roofline"          : the by-time dominant call of the step -- the residual-block backward at the widest level
                         (tt_wide_rb_bwd, C = 32: k_wrb_bwd_a + k_wrb_dxw + k_wrb_reduce, 18 calls per step):
                         algorithmic bytes (dy, x read, dx written once, bf16) / average call time measured with HIP events on the
@@ -161,6 +168,7 @@ def make_train_step(model, opt, world, overlap=True, autocast=True, autocast_dty
             l_trn = compute_transcription_loss(head(transcription), target, True)
             l_sp, l_sc = compute_consistency_loss(head(trn_rec), head(trn_scr), head(trn_coeffs))
             total = l_rec + l_trn + (l_sp + l_sc)
+            state['losses'] = (l_rec, l_trn, l_sp, l_sc)          # for --dump-outputs (references only: no work on the device)
             opt.zero_grad()
             total.backward()
         if sync is not None:
@@ -399,6 +407,28 @@ def cpu_baseline(mc, latent, seconds_budget=15.0, config0=False):
                 s_per_step=step_s, legs_s={k: v / n for k, v in legs.items()})
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6          # --dump-outputs: sample above 60 MB in all, so the files (.npy headers included) stay below 64 MB
+
+
+def write_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: each tensor of ``arrays`` (name -> tensor) as out_dir/<name>.npy in float32 (float64 stays float64).  When the
+    whole set exceeds DUMP_LIMIT_BYTES, every array larger than its even share is replaced by a sample of that many elements: flat
+    indices drawn without replacement by a generator seeded with ``seed`` and the array's position, kept in increasing order -- the
+    same elements for the same shapes in every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    share = DUMP_LIMIT_BYTES // max(1, len(host))
+    for i, (name, a) in enumerate(host.items()):
+        if total > DUMP_LIMIT_BYTES and a.nbytes > share:
+            idx = np.random.default_rng([seed, i]).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def bench_inference(model, args, rank, world, dev, steps=None, warmup=None, emit=True, autocast=False, dtype=None):
     """BASELINE.json configs[1]: model.transcribe(audio) + model.reconstruct(audio), batch x 3 s clips (secondary line).
     autocast=True: the same calls inside torch.autocast (16-bit channels-last path of element type ``dtype``, default bfloat16) -- what a
@@ -426,6 +456,8 @@ def bench_inference(model, args, rank, world, dev, steps=None, warmup=None, emit
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     model.train(was_training)
+    if emit and rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, {'activations': act, 'reconstruction': rec})
     ms = 1000.0 * elapsed / steps
     line = dict(metric='audio-seconds/s inference throughput, transcribe()+reconstruct() (9oct x 60bpo, 3s@22.05kHz)',
                 value=world * batch * SECS_PER_CLIP / (elapsed / steps), unit='audio-seconds/s', n_gpus=world,
@@ -494,10 +526,16 @@ def main():
     ap.add_argument('--skip-connections', action='store_true',
                     help='time the skip_connections=True model (BASELINE configs[4]) as the main line (profiling; the default line reports it as '
                          '"skip_connections_step")')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure every secondary figure (rooflines, kernel families, host enqueue time, inverse CQT, '
+                         'inference config, fp32 / fp16 / skip-connection steps, core-capped run, CPU baselines, N > 1 overlap); '
+                         'off: the headline line only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (float32; arrays sampled above 60 MB in all, files under 64 MB)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--timed-only', action='store_true',
-                    help='skip the untimed legs (instrumented family steps, inverse CQT, inference config, CPU baselines): for rocprofv3 runs whose '
-                         'kernel totals should divide by warmup + steps')
+                    help='with --full: skip the untimed legs (instrumented family steps, inverse CQT, inference config, CPU baselines): for rocprofv3 '
+                         'runs whose kernel totals should divide by warmup + steps')
     ap.add_argument('--cores', type=int, default=None,
                     help='restrict this process to K host cores (applied at import, before torch; see _apply_core_cap)')
     ap.add_argument('--capped-run', choices=('auto', 'on', 'off'), default='auto',
@@ -565,16 +603,24 @@ def main():
     key, key16, keyb = 'resblock_fwd_C%d' % C, 'wide_rb_fwd_C%d' % C, 'wide_rb_bwd_C%d' % C
     keyb_half = 'wide_rb_bwd_C%d' % (C // 2)              # the level below: its backward runs as the one-pass strip kernel
     keyb_narrow = ['wide_rb_bwd_C%d' % c for c in (C // 8, C // 4)]      # the narrow levels: k_nrb_bwd_fused (the largest family of the step)
-    _hip.EVENT_KEYS = {key, key16, keyb, keyb_half, *keyb_narrow, 'cqt_forward'}   # the timed region brackets only the roofline calls
-    _hip.EVENT_LOG = {}
+    if args.full:
+        _hip.EVENT_KEYS = {key, key16, keyb, keyb_half, *keyb_narrow, 'cqt_forward'}   # the timed region brackets only the roofline calls
+        _hip.EVENT_LOG = {}
     t0 = time.perf_counter()
     for _ in range(args.steps):
         total = step_fn(audio, target)
     sync()
     elapsed = time.perf_counter() - t0
     peak_gb = torch.cuda.max_memory_allocated() / 1e9            # weights + optimizer + every tensor saved for backward
-    events = _hip.EVENT_LOG
+    events = _hip.EVENT_LOG or {}
     _hip.EVENT_LOG = None
+    _hip.EVENT_KEYS = None
+    if rank == 0 and args.dump_outputs:
+        # before any untimed leg of --full steps the model again: the loss terms, the parameters after the last timed update and its gradient
+        l_rec, l_trn, l_sp, l_sc = step_fn.state['losses']
+        write_outputs(args.dump_outputs, dict(loss_total=total.reshape(1), loss_reconstruction=l_rec.reshape(1), loss_transcription=l_trn.reshape(1),
+                                              loss_consistency_spectral=l_sp.reshape(1), loss_consistency_score=l_sc.reshape(1),
+                                              flat_param=opt.flat_param, flat_grad=opt.flat_grad))
     rank_ms = 1000.0 * elapsed / args.steps
     per_rank_ms = [rank_ms]
     if multi:
@@ -586,6 +632,23 @@ def main():
         elapsed = max(float(g.item()) for g in gathered)
     ms = 1000.0 * elapsed / args.steps
     value = world * args.batch * SECS_PER_CLIP / (elapsed / args.steps)
+    line = dict(metric='audio-seconds/s training throughput (9oct x 60bpo, 3s@22.05kHz)', value=value,
+                unit='audio-seconds/s', n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=ms,
+                higher_is_better=True, scaling='weak', vs_baseline=None, dtype=train_dtype, data='synthetic',
+                config=dict(workload='full train step (CQT x2 + AE fwd/bwd with consistency + 3 losses + clip + AdamW), '
+                                     'model_complexity=%d latent=%d%s, %d clips x 3 s per GPU%s'
+                                     % (args.mc, args.latent, ' skip_connections=True' if args.skip_connections else '', args.batch, ', under torch.autocast like reference experiments/train.py:415 '
+                                        '(bf16 MFMA conv path of BASELINE config[2]; fp32 master weights, losses and optimizer)'
+                                        if args.precision == 'auto' else ''),
+                            global_batch=world * args.batch, parallelism='dp%d' % world))
+    if not args.full:
+        if rank == 0:
+            line.update(peak_memory_gb=peak_gb, per_rank_ms=per_rank_ms, final_loss=float(total.detach()))
+            print(json.dumps(line))
+        if multi:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- the host side of a step (round-5 verdict, weak #12): how long Python + autograd need to ENQUEUE a step, with no sync inside --
     # wall time until the last launch of `n_enq` steps has returned, next to the synced wall time of the same steps.  host_over_gpu << 1:
@@ -907,7 +970,7 @@ def main():
             # the same timed loop in a CHILD process restricted to two host cores from its first instruction (`--cores 2`: affinity set
             # before torch is imported; this parent only waits) -- what a rank gets when eight of them share this box's cores
             import subprocess
-            cmd = [sys.executable, os.path.abspath(__file__), '--cores', '2', '--timed-only', '--steps', str(max(args.steps, 10)), '--warmup', '3',
+            cmd = [sys.executable, os.path.abspath(__file__), '--cores', '2', '--full', '--timed-only', '--steps', str(max(args.steps, 10)), '--warmup', '3',
                    '--batch', str(args.batch), '--mc', str(args.mc), '--latent', str(args.latent)]
             try:
                 r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
@@ -918,21 +981,12 @@ def main():
                 capped = dict(cores=child['host']['host_cores'], ms_per_step=child['ms_per_step'], vs_uncapped=child['ms_per_step'] / ms,
                               host_enqueue_ms=child['host']['host_enqueue_ms'], host_over_gpu=child['host']['host_over_gpu'],
                               steps=child['steps'], warmup=child['warmup'],
-                              note='python bench.py --cores 2 --timed-only as a child process: the whole train step with the host side on two cores')
+                              note='python bench.py --cores 2 --full --timed-only as a child process: the whole train step with the host side on two cores')
         base = base0 = None
         if not args.no_cpu_baseline and not args.timed_only and world == 1:
             base = cpu_baseline(args.mc, args.latent)
             base0 = cpu_baseline(1, None, config0=True)
-        line = dict(metric='audio-seconds/s training throughput (9oct x 60bpo, 3s@22.05kHz)', value=value,
-                    unit='audio-seconds/s', n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=ms,
-                    higher_is_better=True, scaling='weak', vs_baseline=None, dtype=train_dtype, data='synthetic',
-                    config=dict(workload='full train step (CQT x2 + AE fwd/bwd with consistency + 3 losses + clip + AdamW), '
-                                         'model_complexity=%d latent=%d%s, %d clips x 3 s per GPU%s'
-                                         % (args.mc, args.latent, ' skip_connections=True' if args.skip_connections else '', args.batch, ', under torch.autocast like reference experiments/train.py:415 '
-                                            '(bf16 MFMA conv path of BASELINE config[2]; fp32 master weights, losses and optimizer)'
-                                            if args.precision == 'auto' else ''),
-                                global_batch=world * args.batch, parallelism='dp%d' % world),
-                    roofline=roof, roofline_fwd=roof_fwd if roof_fwd is not roof else None, roofline_onepass_bwd=roof_onepass,
+        line.update(roofline=roof, roofline_fwd=roof_fwd if roof_fwd is not roof else None, roofline_onepass_bwd=roof_onepass,
                     roofline_narrow_bwd=roof_narrow or None, host=host_info, core_capped_run=capped, roofline_cqt=cqt, roofline_cqt_inv=cqt_inv, families=families, whole_step=whole,
                     peak_memory_gb=peak_gb, inference_config1=infer, fp32_train_step=fp32_step, fp16_train_step=fp16_step, skip_connections_step=skip_step, per_rank_ms=per_rank_ms, allreduce_ms=allreduce_ms, overlap=overlap_info, cpu_baseline=base, cpu_baseline_config0=base0,
                     final_loss=float(total.detach()))

@@ -369,8 +369,12 @@ int tt_gemm(const float* A, const float* Bm, float* C, const float* bias,
             int batch, int64_t sa, int64_t sb, int64_t sc, int reduce_batch,
             float alpha, float beta, int bias_mode, int bias_div, int act, void* stream);
 
-/* out[c] += sum over (b, inner) of x[b, c, inner]; x viewed as (B, C, inner). */
+/* out[c] += sum over (b, inner) of x[b, c, inner]; x viewed as (B, C, inner).  The partial sums meet in atomics (low bits vary from
+ * run to run). */
 int tt_channel_sum(const float* x, float* out, int B, int C, int64_t inner, void* stream);
+/* The same sum in a fixed order, bit-identical from run to run (version 7): ws is device scratch of at least 2 C + 2048 floats,
+ * free until the call's stream has run it. */
+int tt_channel_sum_ws(const float* x, float* out, int B, int C, int64_t inner, float* ws, void* stream);
 
 /* y = a + s[idx] * b  (skip connections, modules.py:112 and :569-589); s may be NULL (scale 1),
  * a may be NULL (treated as 0). */

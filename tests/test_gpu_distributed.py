@@ -113,14 +113,13 @@ NCCL_SCRIPT = textwrap.dedent('''
 
 
 @pytest.mark.gpu
-def test_rccl_allreduce_smoke_when_two_gpus_present():
+def test_rccl_allreduce_smoke_when_two_gpus_present(tmp_path):
     """The 'nccl' (= RCCL over xGMI) branch, one process per GPU through torchrun; skipped on a 1-GPU box."""
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip('needs >= 2 GPUs (the test box has one): the RCCL branch runs in the driver\'s multi-GPU bench')
     n = min(torch.cuda.device_count(), 8)
-    path = os.path.join(ROOT, 'gpurun_out', 'nccl_smoke.py')
-    os.makedirs(os.path.dirname(path), exist_ok=True)
+    path = str(tmp_path / 'nccl_smoke.py')
     with open(path, 'w') as f:
         f.write(NCCL_SCRIPT)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
@@ -149,7 +148,7 @@ def test_rccl_single_rank_next_to_the_hip_library():
     with socket.socket() as s_:
         s_.bind(('127.0.0.1', 0))
         port = s_.getsockname()[1]
-    argv = ['--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '2', '--no-cpu-baseline']
+    argv = ['--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '2', '--no-cpu-baseline', '--full']
     out = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
                           '--master-port', str(port), os.path.join(ROOT, 'bench.py')] + argv, env=env, capture_output=True, text=True,
                          timeout=900)
@@ -187,7 +186,7 @@ def test_two_host_cores_keep_up_with_the_gpu_step():
     within 5 % of the unrestricted run's, and in both the host must finish enqueueing well before the GPU finishes computing.
     """
     import json
-    argv = ['--timed-only', '--steps', '8', '--warmup', '3']
+    argv = ['--full', '--timed-only', '--steps', '8', '--warmup', '3']
     runs = {}
     for name, extra in (('all cores', []), ('two cores', ['--cores', '2'])):
         out = _bench(*(extra + argv))
@@ -207,7 +206,7 @@ def test_bare_bench_gpus2_launches_two_ranks():
     """`python bench.py --gpus 2` with no WORLD_SIZE starts its own two ranks (fresh children through torch.distributed.run) and
     reports n_gpus = 2 -- it used to benchmark ONE GPU silently (round-3 verdict).  gloo so that both ranks can share the box's GPU."""
     import json
-    out = _bench('--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '2', '--no-cpu-baseline', TTRAP_DIST_BACKEND='gloo')
+    out = _bench('--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '2', '--no-cpu-baseline', '--full', TTRAP_DIST_BACKEND='gloo')
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, out.stdout[-2000:]

@@ -757,7 +757,7 @@ def test_latent_heads_stagewise(CT, D, B, T):
     wdb, bdb = w.cuda().requires_grad_(True), be.cuda().requires_grad_(True)
     ops.LatEnc16Fn.apply(x16b, wdb, bdb, _Link()).backward(dlat.cuda())
     _close16(_f64(x16b.grad), torch.einsum('dk,bdt->bkt', W2, dlr).view(B, CT, E, T) * _gate(_f64(x16b.detach())), 'dtop gated')
-    assert torch.equal(wdb.grad, wd.grad) and _rel(bdb.grad.double(), bdv.grad.double()) < 1e-6       # (tt_channel_sum ends in fp32 atomics)
+    assert torch.equal(wdb.grad, wd.grad) and _rel(bdb.grad.double(), bdv.grad.double()) < 1e-6       # (two routes, summed in different orders)
     if D < (48 if CT == 32 else 144):
         link = ops.GateLink()
         zd3 = z.cuda().requires_grad_(True)

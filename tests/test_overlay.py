@@ -2,7 +2,9 @@
 The package is an OVERLAY on a reference checkout: with ``timbre-trap_amd`` in front of the reference on
 ``sys.path``, the import block of reference experiments/train.py:1-9 and evaluate.py:1-3 must resolve -- framework from this
 package, dataset wrappers / constants from the reference.  Third-party packages the image lacks are stubbed for import only.
-Skipped where the reference is not present (e.g. the GPU box).
+The reference is the checkout named by TTRAP_REFERENCE, or else a stand-in written by the test: the reference's module layout and
+the names those imports take from it (``timbre_trap`` without ``__init__.py``, ``utils.data.constants``, the dataset classes),
+with empty classes for bodies.
 """
 
 import os
@@ -13,7 +15,38 @@ import textwrap
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFERENCE = '/root/reference'
+
+# the stand-in reference: relative path -> source.  Only names and their places: what the overlay has to find, nothing it would run
+STAND_IN = {
+    'timbre_trap/utils/__init__.py': '',
+    'timbre_trap/utils/data.py': "__all__ = ['constants']\n\n\nclass constants(object):\n    KEY_AUDIO = 'audio'\n    KEY_GROUND_TRUTH = 'ground-truth'\n",
+    'timbre_trap/datasets/__init__.py': '',
+    'timbre_trap/datasets/BaseDataset.py': ('from timbre_trap.utils.data import *\n\n\nclass BaseDataset(object):\n    pass\n\n\n'
+                                            'class ComboDataset(object):\n    pass\n\n\nclass StemMixingDataset(ComboDataset):\n    pass\n'),
+    'timbre_trap/datasets/AudioDataset.py': 'from . import BaseDataset\n\n\nclass AudioDataset(BaseDataset):\n    pass\n',
+    'timbre_trap/datasets/PitchDataset.py': 'from . import BaseDataset\n\n\nclass PitchDataset(BaseDataset):\n    pass\n',
+    'timbre_trap/datasets/MPEDataset.py': 'from . import AudioDataset, PitchDataset\n\n\nclass MPEDataset(AudioDataset, PitchDataset):\n    pass\n',
+    'timbre_trap/datasets/NoteDataset.py': 'from . import PitchDataset\n\n\nclass NoteDataset(PitchDataset):\n    pass\n',
+    'timbre_trap/datasets/AMTDataset.py': 'from . import MPEDataset, NoteDataset\n\n\nclass AMTDataset(MPEDataset, NoteDataset):\n    pass\n',
+}
+for _pkg, _base, _names in (('MixedMultiPitch', 'MPEDataset', ('URMP', 'Bach10', 'Su', 'TRIOS')),
+                            ('SoloMultiPitch', 'MPEDataset', ('URMP', 'MedleyDB_Pitch', 'GuitarSet')),
+                            ('AudioMixtures', 'AudioDataset', ('MedleyDB', 'FMA')),
+                            ('AudioStems', 'AudioDataset', ('MedleyDB',))):
+    STAND_IN['timbre_trap/datasets/%s/__init__.py' % _pkg] = 'from .. import %s\n' % _base + ''.join(
+        '\n\nclass %s(%s):\n    pass\n' % (n, _base) for n in _names)
+
+
+def _reference(tmp_path):
+    """The reference checkout the overlay sits on: TTRAP_REFERENCE, or the stand-in written under tmp_path."""
+    if os.environ.get('TTRAP_REFERENCE'):
+        return os.environ['TTRAP_REFERENCE']
+    ref = tmp_path / 'reference'
+    for rel, src in STAND_IN.items():
+        (ref / rel).parent.mkdir(parents=True, exist_ok=True)
+        (ref / rel).write_text(src)
+    return str(ref)
+
 
 SCRIPT = textwrap.dedent('''
     import sys, types
@@ -53,13 +86,14 @@ SCRIPT = textwrap.dedent('''
     import torch
     assert issubclass(DataParallel, torch.nn.DataParallel)
     print('OVERLAY_OK')
-''') % (os.path.join(ROOT, 'timbre-trap_amd'), REFERENCE, os.path.join(ROOT, 'timbre-trap_amd'), REFERENCE, REFERENCE)
+''')
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, 'timbre_trap')), reason='no reference checkout on this machine')
-def test_reference_script_imports_resolve_through_the_overlay():
+def test_reference_script_imports_resolve_through_the_overlay(tmp_path):
+    ref = _reference(tmp_path)
+    script = SCRIPT % (os.path.join(ROOT, 'timbre-trap_amd'), ref, os.path.join(ROOT, 'timbre-trap_amd'), ref, ref)
     env = {k: v for k, v in os.environ.items() if k != 'PYTHONPATH'}
-    out = subprocess.run([sys.executable, '-c', SCRIPT], capture_output=True, text=True, timeout=300, env=env)
+    out = subprocess.run([sys.executable, '-c', script], capture_output=True, text=True, timeout=300, env=env)
     assert out.returncode == 0 and 'OVERLAY_OK' in out.stdout, out.stdout[-1500:] + out.stderr[-3000:]
 
 

@@ -133,6 +133,9 @@ __device__ __forceinline__ unsigned lds_addr(const unsigned char* p) {
 // shape of the partial-sum reduce kernels: a block of 1024 threads = REL consecutive dump elements x RSL slices of the contributors
 // (each thread keeps eight loads in flight; 16 x 64 puts 600+ blocks on the chip where 64 x 16 left a third of the CUs idle)
 constexpr int REL = 16, RSL = 64;
+// the narrow levels' reduce (k_nrb_reduce) has only 9 C^2 + C^2 + 2C output elements: NREL elements x NRSL slices per block keeps
+// 42 / 164 blocks on the chip at C = 4 / 8 (REL x RSL would leave 11 / 41)
+constexpr int NREL = 4, NRSL = 256;
 
 inline int grid_for(int ntiles, int lds_bytes, int max_per_cu) {
     int per = lds_bytes > 0 ? (160 * 1024) / lds_bytes : max_per_cu;

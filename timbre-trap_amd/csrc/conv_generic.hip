@@ -237,9 +237,11 @@ __global__ __launch_bounds__(256) void k_elu_bwd(const float* __restrict__ dy, c
     }
 }
 
-// out[c] += sum_{b, inner} x[b][c][inner] ; grid (C, chunks)
-__global__ __launch_bounds__(256) void k_channel_sum(const float* __restrict__ x, float* __restrict__ out, int B, int C,
-                                                     long inner) {
+// out[c] += sum_{b, inner} x[b][c][inner] ; grid (C, chunks).  part == nullptr: the chunks meet in atomicAdd (tt_channel_sum, arrival
+// order); else the sum of chunk j of channel c goes to part[j * C + c] and k_channel_sum_fin adds a channel's chunks in ascending order
+// (tt_channel_sum_ws: bit-identical from run to run)
+__global__ __launch_bounds__(256) void k_channel_sum(const float* __restrict__ x, float* __restrict__ out, float* __restrict__ part, int B,
+                                                     int C, long inner) {
     __shared__ float red[4];
     const int c = blockIdx.x;
     float acc = 0.f;
@@ -252,7 +254,18 @@ __global__ __launch_bounds__(256) void k_channel_sum(const float* __restrict__ x
     acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(out + c, red[0] + red[1] + red[2] + red[3]);
+    if (threadIdx.x == 0) {
+        if (part) part[(long)blockIdx.y * C + c] = (red[0] + red[1]) + (red[2] + red[3]);
+        else atomicAdd(out + c, red[0] + red[1] + red[2] + red[3]);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_channel_sum_fin(const float* __restrict__ part, float* __restrict__ out, int C, int chunks) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    float sum = 0.f;
+    for (int j = 0; j < chunks; ++j) sum += part[(long)j * C + c];
+    out[c] += sum;
 }
 
 __global__ __launch_bounds__(256) void k_scaled_add(const float* __restrict__ a, const float* __restrict__ b,
@@ -659,7 +672,19 @@ extern "C" int tt_elu_bwd(const float* dy, const float* y, float* g, int64_t n, 
 extern "C" int tt_channel_sum(const float* x, float* out, int B, int C, int64_t inner, void* stream) {
     if (!x || !out || B <= 0 || C <= 0 || inner <= 0) return TT_E_BADARG;
     int chunks = grid1d((long)B * inner, 256 * 8, 2048 / (C > 2048 ? 2048 : C) + 1);
-    hipLaunchKernelGGL(k_channel_sum, dim3(C, chunks), dim3(256), 0, tt_stream(stream), x, out, B, C, (long)inner);
+    hipLaunchKernelGGL(k_channel_sum, dim3(C, chunks), dim3(256), 0, tt_stream(stream), x, out, nullptr, B, C, (long)inner);
+    TT_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int tt_channel_sum_ws(const float* x, float* out, int B, int C, int64_t inner, float* ws, void* stream) {
+    if (!x || !out || !ws || B <= 0 || C <= 0 || inner <= 0) return TT_E_BADARG;
+    // chunks <= 2048 / C + 1 (C <= 2048) or 2: C * chunks <= 2 C + 2048, the size of ws (include/ttrap.h)
+    int chunks = grid1d((long)B * inner, 256 * 8, 2048 / (C > 2048 ? 2048 : C) + 1);
+    hipStream_t st = tt_stream(stream);
+    hipLaunchKernelGGL(k_channel_sum, dim3(C, chunks), dim3(256), 0, st, x, out, ws, B, C, (long)inner);
+    TT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_channel_sum_fin, dim3((C + 255) / 256), dim3(256), 0, st, ws, out, C, chunks);
     TT_LAUNCH_CHECK();
     return 0;
 }

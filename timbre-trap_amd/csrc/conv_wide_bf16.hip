@@ -21,9 +21,9 @@
 //                                  dA1 = dh1 ELU'(a1); dW2, db1, db2 partials
 //   k_wrb_wgrad<C,D>               dW1[co][ci][tap] = sum_pix dA1[co][pix] x[ci][pix + tap]: K = pixels, both operands by
 //                                  LDS transpose reads (ds_read_b64_tr_b16) from channel-innermost images
-//   k_wrb_reduce<C>                sums the per-wave register dumps into the fp32 gradients (+=) in a fixed order: no atomics at the
-//                                  wide levels (the narrow levels' k_nrb_reduce below meets the 16 / C diagonal contributions of a
-//                                  dW1 element in atomicAdd: run-to-run differences at fp32 rounding, tests/test_gpu_determinism.py)
+//   k_wrb_reduce<C>                sums the per-wave register dumps into the fp32 gradients (+=) in a fixed order: no atomics (the
+//                                  narrow levels' k_nrb_reduce below also adds the 16 / C diagonal contributions of a dW1 element in a
+//                                  fixed order: bit-identical from run to run, tests/test_gpu_determinism.py)
 #include "wide_common.h"
 
 namespace {
@@ -1749,41 +1749,58 @@ __global__ __launch_bounds__(NT) void k_nrb_dxw(const e16* __restrict__ x, const
     for (int i = tid; i < 2304; i += NT) pw[i] = (red[i] + red[2304 + i]) + (red[2 * 2304 + i] + red[3 * 2304 + i]);
 }
 
+// Every sum in a fixed order (bit-reproducible from run to run).  The first 9 C^2 elements are the dW1 entries (tap k, co c, ci c2),
+// each the sum of its 16 / C diagonal dump elements (D row 4g + r = (pixel-in-slot s, channel c), column n = (s, c2)) over every
+// contributing wave; then dW2, db1, db2.  A block = NREL elements x NRSL slices of the contributors, joined by a fixed LDS tree.
 template <int C>
 __global__ __launch_bounds__(1024) void k_nrb_reduce(RedBatch batch) {
     const RedArgs& ar = batch.a[blockIdx.y];
-    constexpr int WDUMP = 9 * 256, ADUMP = C * C + 2 * C;
-    __shared__ float red[RSL][REL];
-    const int el = threadIdx.x % REL, sl = threadIdx.x / REL;
-    const int e = blockIdx.x * REL + el;
-    float part[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (e < WDUMP) {
+    constexpr int WDUMP = 9 * 256, NW = 9 * C * C, ADUMP = C * C + 2 * C, NS = 16 / C;
+    __shared__ float red[NRSL][NREL];
+    const int el = threadIdx.x % NREL, sl = threadIdx.x / NREL;
+    const int e = blockIdx.x * NREL + el;
+    float part[4] = {0.f, 0.f, 0.f, 0.f};
+    if (e < NW) {
+        const int k = e / (C * C), c = (e / C) % C, c2 = e % C;
+        int de[NS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int m = s * C + c, n = s * C + c2;
+            de[s] = k * 256 + (m & 3) * 64 + (m >> 2) * 16 + n;
+        }
         const int stride = ar.one_dump ? 4 : 1;                  // one_dump: only wave slot 0 of every workgroup holds data
         const int ncontrib = ar.one_dump ? ar.gw : ar.gw * 4;
-        for (int j0 = sl; j0 < ncontrib; j0 += 8 * RSL)
+        for (int j0 = sl; j0 < ncontrib; j0 += 4 * NRSL)
 #pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (j0 + RSL * u < ncontrib) part[u] += ar.pw[(long)(j0 + RSL * u) * stride * WDUMP + e];
-    } else if (e < WDUMP + ADUMP) {
+            for (int u = 0; u < 4; ++u)
+                if (j0 + NRSL * u < ncontrib) {
+                    const float* src = ar.pw + (long)(j0 + NRSL * u) * stride * WDUMP;
+                    float v = 0.f;
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) v += src[de[s]];
+                    part[u] += v;
+                }
+    } else if (e < NW + ADUMP) {
         const int ncontrib = ar.ga;
-        for (int j0 = sl; j0 < ncontrib; j0 += 8 * RSL)
+        for (int j0 = sl; j0 < ncontrib; j0 += 4 * NRSL)
 #pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (j0 + RSL * u < ncontrib) part[u] += ar.pa[(long)(j0 + RSL * u) * ADUMP + (e - WDUMP)];
+            for (int u = 0; u < 4; ++u)
+                if (j0 + NRSL * u < ncontrib) part[u] += ar.pa[(long)(j0 + NRSL * u) * ADUMP + (e - NW)];
     }
-    red[sl][el] = ((part[0] + part[1]) + (part[2] + part[3])) + ((part[4] + part[5]) + (part[6] + part[7]));
+    red[sl][el] = (part[0] + part[1]) + (part[2] + part[3]);
     __syncthreads();
-    if (sl != 0) return;
-    float sum = 0.f;
 #pragma unroll
-    for (int i = 0; i < RSL; ++i) sum += red[i][el];
-    if (e < WDUMP) {
-        const int k = e >> 8, r = (e >> 6) & 3, lane = e & 63, g = lane >> 4, n = lane & 15;
-        // D row 4g + r = (pixel-in-slot s, channel c), column n = (s', c'): keep s == s'
-        const int m = 4 * g + r, s = m / C, c = m - s * C, s2 = n / C, c2 = n - s2 * C;
-        if (s == s2) atomicAdd(ar.dw1 + (c * C + c2) * 9 + k, sum * ar.scale);   // 16 / C contributions per element
-    } else if (e < WDUMP + ADUMP) {
-        const int q = e - WDUMP;
+    for (int w = NRSL / 2; w > 0; w >>= 1) {
+        if (sl < w) red[sl][el] += red[sl + w][el];
+        __syncthreads();
+    }
+    if (sl != 0) return;
+    const float sum = red[0][el];
+    if (e < NW) {
+        const int k = e / (C * C), c = (e / C) % C, c2 = e % C;
+        ar.dw1[(c * C + c2) * 9 + k] += sum * ar.scale;
+    } else if (e < NW + ADUMP) {
+        const int q = e - NW;
         float* dst = q < C * C ? ar.dw2 + q : (q < C * C + C ? ar.db1 + (q - C * C) : ar.db2 + (q - C * C - C));
         *dst += sum * ar.scale;
     }
@@ -1853,8 +1870,8 @@ int launch_nbwd(const e16* x, const e16* h1, const e16* dy, const float* w1, con
         }
         TT_LAUNCH_CHECK();
         RedArgs ra{part_w, gf, part_a, gf, dw1, db1, dw2, db2, 0, 1};
-        constexpr int total = 9 * 256 + C * C + 2 * C;
-        return reduce_or_defer(k_nrb_reduce<C>, total, ra, st);
+        constexpr int total = 9 * C * C + C * C + 2 * C;
+        return reduce_or_defer(k_nrb_reduce<C>, total, ra, st, NREL);
     }
     const long ngroups = (npix + 63) / 64;
     const long want = (ngroups + 3) / 4;
@@ -1877,8 +1894,8 @@ int launch_nbwd(const e16* x, const e16* h1, const e16* dy, const float* w1, con
         hipLaunchKernelGGL(kx, dim3(gx), dim3(NT), LDS, st, x, da1, dy, w1, dx, part_w, B, H, T, tiles_h, tiles_t, ntiles);
         TT_LAUNCH_CHECK();
         RedArgs ra{part_w, gx, part_a, grid, dw1, db1, dw2, db2, 0, 1};
-        constexpr int total = 9 * 256 + C * C + 2 * C;
-        return reduce_or_defer(k_nrb_reduce<C>, total, ra, st);
+        constexpr int total = 9 * C * C + C * C + 2 * C;
+        return reduce_or_defer(k_nrb_reduce<C>, total, ra, st, NREL);
     }
     if (int rc = launch_nconv<C, D, 1, false>(da1, w1, nullptr, nullptr, nullptr, dy, dx, nullptr, B, H, T, st)) return rc;
     using W = NG<C, D>;
@@ -1892,8 +1909,8 @@ int launch_nbwd(const e16* x, const e16* h1, const e16* dy, const float* w1, con
     hipLaunchKernelGGL(kw, dim3(gw), dim3(NT), W::LDS_BYTES, st, x, da1, part_w, B, H, T, tiles_h, tiles_t, ntiles);
     TT_LAUNCH_CHECK();
     RedArgs ra{part_w, gw, part_a, grid, dw1, db1, dw2, db2};
-    constexpr int total = 9 * 256 + C * C + 2 * C;
-    return reduce_or_defer(k_nrb_reduce<C>, total, ra, st);
+    constexpr int total = 9 * C * C + C * C + 2 * C;
+    return reduce_or_defer(k_nrb_reduce<C>, total, ra, st, NREL);
 }
 
 template <int C>
@@ -2090,8 +2107,9 @@ static int level_bwd(int gate, int nblocks, const void* const* x, const void* co
         TT_LAUNCH_CHECK();
     }
     if (batch.n > 0) {
-        const int total = (C <= 8 ? 9 * 256 : 9 * C * C) + C * C + 2 * C;
-        const dim3 grid((total + REL - 1) / REL, batch.n);
+        const int total = 9 * C * C + C * C + 2 * C;
+        const int per_block = C <= 8 ? NREL : REL;              // k_nrb_reduce : k_wrb_reduce
+        const dim3 grid((total + per_block - 1) / per_block, batch.n);
         switch (C) {
             case 4: hipLaunchKernelGGL(k_nrb_reduce<4>, grid, dim3(1024), 0, st, batch); break;
             case 8: hipLaunchKernelGGL(k_nrb_reduce<8>, grid, dim3(1024), 0, st, batch); break;

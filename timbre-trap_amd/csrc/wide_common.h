@@ -163,7 +163,7 @@ __device__ __forceinline__ void skipj_finish(float dot, const SkipJ& sj) {
     if ((threadIdx.x & 63) == 0) atomicAdd(sj.dw, dot * sj.unscale);
 }
 
-template <class Kernel> inline int reduce_or_defer(Kernel kern, int total, const RedArgs& ra, hipStream_t st) {
+template <class Kernel> inline int reduce_or_defer(Kernel kern, int total, const RedArgs& ra, hipStream_t st, int per_block = REL) {
     if (ttx_red_defer) {
         RedBatch* b = static_cast<RedBatch*>(ttx_red_defer);
         if (b->n >= 4) return TT_E_BADARG;
@@ -172,7 +172,7 @@ template <class Kernel> inline int reduce_or_defer(Kernel kern, int total, const
     }
     RedBatch one;
     one.a[0] = ra; one.n = 1;
-    hipLaunchKernelGGL(kern, dim3((total + REL - 1) / REL, 1), dim3(1024), 0, st, one);
+    hipLaunchKernelGGL(kern, dim3((total + per_block - 1) / per_block, 1), dim3(1024), 0, st, one);
     TT_LAUNCH_CHECK();
     return 0;
 }

@@ -121,6 +121,7 @@ _PROTOS = {
     'tt_tconv_bwd': (c_int, [P, P, P, P, P, P, P, P, I, I, I, I, I, P]),
     'tt_gemm': (c_int, [P, P, P, P, I, I, I, I, I, L, L, L, I, L, L, L, I, F_, F_, I, I, I, P]),
     'tt_channel_sum': (c_int, [P, P, I, I, L, P]),
+    'tt_channel_sum_ws': (c_int, [P, P, I, I, L, P, P]),
     'tt_scaled_add': (c_int, [P, P, P, I, P, L, P]),
     'tt_window_ola': (c_int, [P, P, P, L, I, I, I, L, P]),
     'tt_dot': (c_int, [P, P, P, L, P]),

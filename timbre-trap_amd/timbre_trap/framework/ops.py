@@ -249,7 +249,7 @@ class ConvFn(torch.autograd.Function):
                                           cfg.stride, 1, 1, 0, 0,
                                           Cout * KH * KW, KH * KW, KW, 1, st), 'tt_conv2d_wgrad(T)')
         if db is not None:
-            check(lib.tt_channel_sum(ptr(g), ptr(db), B, Cout, Hout * T, st), 'tt_channel_sum')
+            _channel_sum(g, db, B, Cout, Hout * T, st)
         return dx, rw, rb, None
 
 
@@ -304,6 +304,12 @@ class ScaleFn(torch.autograd.Function):
             ds = torch.zeros_like(s)
             check(lib.tt_dot(ptr(dy), ptr(e), _off(ds, ctx.idx), e.numel(), st), 'tt_dot')
         return de, ds, None
+
+
+def _channel_sum(x, db, B, C, inner, st):
+    """db[c] += sum of x viewed as (B, C, inner) over b and inner (tt_channel_sum_ws: fixed summation order, through a workspace)."""
+    ws = torch.empty(2 * C + 2048, dtype=torch.float32, device=x.device)
+    check(_hip.lib().tt_channel_sum_ws(ptr(x), ptr(db), B, C, inner, ptr(ws), st), 'tt_channel_sum_ws')
 
 
 def _grad_target(p):
@@ -1597,7 +1603,7 @@ class LatentEncodeFn(torch.autograd.Function):
                               1.0, 1.0, 0, 1, ACT_NONE, st), 'tt_gemm(convlat wgrad)')
             if ctx.has_bias:
                 db, rb = _grad_target(ctx.params[1])
-                check(lib.tt_channel_sum(ptr(dy), ptr(db), B, D, T, st), 'tt_channel_sum')
+                _channel_sum(dy, db, B, D, T, st)
         return dx, rw, rb
 
 
@@ -1639,7 +1645,7 @@ class LatentDecodeFn(torch.autograd.Function):
                               1.0, 1.0, 0, 1, ACT_NONE, st), 'tt_gemm(dec convin wgrad)')
             if ctx.has_bias:
                 db, rb = _grad_target(ctx.params[1])
-                check(lib.tt_channel_sum(ptr(g), ptr(db), B, C, E * T, st), 'tt_channel_sum')
+                _channel_sum(g, db, B, C, E * T, st)
         return dz, rw, rb
 
 
@@ -1690,7 +1696,7 @@ class LatEnc16Fn(torch.autograd.Function):
             dw, rw = _grad_target(ctx.params[0])
             check(lib.tt_latent16_wgrad(ptr(dy), D, 0.0, ptr(x), None, ptr(dw), None, ptr(ws), B, CT, D, E, T, st), 'tt_latent16_wgrad')
             db, rb = _grad_target(ctx.params[1])
-            check(lib.tt_channel_sum(ptr(dy), ptr(db), B, D, T, st), 'tt_channel_sum')
+            _channel_sum(dy, db, B, D, T, st)
         return dx, rw, rb, None
 
 

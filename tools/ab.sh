@@ -6,7 +6,7 @@
 # A variant is a string of environment assignments ("" = the defaults), e.g. "TTRAP_SKIP_FOLD=0" or "TTRAP_LIB=libttrap_x.so"
 # (a library built with tools/build_variant.sh).  The variants run back to back on the same box, REPS rounds (default 2), each as a
 # fresh `python bench.py` process: -m train (default) = `--timed-only` train step, -m infer = `--mode infer` (BASELINE configs[1]),
-# -m skip = the full line's skip_connections_step (slower: runs every secondary leg).  -t: a pytest selection run first WITH EACH
+# -m skip = the `--full` line's skip_connections_step (slower: runs every secondary leg).  -t: a pytest selection run first WITH EACH
 # variant's environment (parity before speed).  Output: gpurun_out/<tag>.txt (one "variant | ms" line per run) -- copy into profiles/.
 tag=$1; shift
 mode=train; reps=2; steps=20; tests=""
@@ -40,7 +40,7 @@ for i in $(seq 1 $reps); do
     case $mode in
       train) args="--timed-only --no-cpu-baseline --steps $steps --warmup 5";;
       infer) args="--mode infer --steps $steps --warmup 3";;
-      skip)  args="--no-cpu-baseline --steps 10 --warmup 5";;
+      skip)  args="--full --no-cpu-baseline --steps 10 --warmup 5";;
     esac
     ms=$(env $v python bench.py $args 2>/dev/null | python -c "$pick" $mode)
     echo "[${v:-defaults}] | $ms ms" >> $out

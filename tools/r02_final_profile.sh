@@ -12,7 +12,7 @@ rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $out/pmc_fetch -o p -- python3 $roo
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $out/pmc_write -o p -- python3 $root/tools/kb_wide.py > $out/pmc_write.log 2>&1
 rocprofv3 --pmc SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_INSTS_VALU SQ_WAIT_ANY --kernel-trace -d $out/pmc_sq -o p -- python3 $root/tools/kb_wide.py > $out/pmc_sq.log 2>&1
 cd $root
-python3 bench.py > $out/bench_default.json 2> $out/bench_default.err
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_steps20.json 2> $out/bench_steps20.err
+python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err
+python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_steps20.json 2> $out/bench_steps20.err
 python3 bench.py --mode infer > $out/bench_infer.json 2> $out/bench_infer.err
 ls $out

@@ -14,8 +14,8 @@ rocprofv3 --kernel-trace --stats -d /tmp/prof_fp32 -o t -- python3 $root/bench.p
 python3 $root/tools/prof_summary.py $(find /tmp/prof_fp32 -name 't_results.db') 6 > $out/fp32_kernel_trace.txt
 python3 $root/tools/prof_families.py $out/fp32_kernel_trace.txt > $out/fp32_families.txt
 cd $root
-python3 bench.py > $out/bench_default.json 2> $out/bench_default.err
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_steps20.json 2> $out/bench_steps20.err
+python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err
+python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_steps20.json 2> $out/bench_steps20.err
 python3 bench.py --mode infer > $out/bench_infer.json 2> $out/bench_infer.err
 fi
 rm -rf /tmp/prof_bf16 /tmp/prof_fp32

@@ -17,8 +17,8 @@ rocprofv3 --kernel-trace --stats -d /tmp/prof_infer -o t -- python3 $root/bench.
 python3 $root/tools/prof_summary.py $(find /tmp/prof_infer -name 't_results.db') 8 > $out/infer_kernel_trace.txt
 rm -rf /tmp/prof_bf16 /tmp/prof_skip /tmp/prof_infer
 cd $root
-python3 bench.py > $out/bench_default.json 2> $out/bench_default.err
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_steps20.json 2> $out/bench_steps20.err
+python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err
+python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_steps20.json 2> $out/bench_steps20.err
 python3 bench.py --mode infer > $out/bench_infer.json 2> $out/bench_infer.err
 export KB_N=3 KB_D=1,2,3
 KB_C=16 KB_WHAT=bwd bash tools/pmc_level.sh r06_C16 > /dev/null 2>&1
