@@ -39,6 +39,10 @@ extern "C" {
 
 #define TT_ACT_NONE 0
 #define TT_ACT_ELU  1
+/* the output nonlinearities of the magnitude variants' decoders (version 8): TimbreTrapMag.decode's relu (modules.py:976),
+ * TimbreTrapMagDB.decode's sigmoid (modules.py:1043); tt_conv2d only */
+#define TT_ACT_RELU    2
+#define TT_ACT_SIGMOID 3
 
 /* Library / build identification. */
 int         tt_version(void);
@@ -91,6 +95,11 @@ int64_t tt_cqt_scratch_bytes(int n_clips, int n_bins, int sum_len);
  * (CQT.encode, used raw by experiments/sonify.py:94). */
 int tt_cqt_forward(const tt_cqt_plan* plan, const float* audio, float* out, void* scratch,
                    int B, int n_blocks, int out_complex, void* stream);
+
+/* The magnitude variants' encoder input (version 8; TimbreTrapMag.encode, modules.py:948: to_magnitude(sliCQ(audio)).unsqueeze(-3)):
+ * audio (B, 1, n_blocks*66150) -> out (B, 1, F, n_blocks*1024) = |c|, written by the band kernel's epilogue -- the two coefficient
+ * planes never reach memory.  Same values as tt_magnitude of tt_cqt_forward's output. */
+int tt_cqt_forward_mag(const tt_cqt_plan* plan, const float* audio, float* out, void* scratch, int B, int n_blocks, void* stream);
 
 /* coeffs (B, 2, F, n_blocks*1024) [or interleaved complex (B,1,F,T) if in_complex] ->
  * audio (B, 1, n_blocks*66150).  normalize != 0 applies cqtwrapper.py:209-211
@@ -164,6 +173,9 @@ int tt_conv2d_wgrad(const float* x, const float* g, float* dw, float* dbias,
 
 /* g = dy * ELU'(a) expressed through the saved OUTPUT y = ELU(a):  ELU' = y > 0 ? 1 : y + 1. */
 int tt_elu_bwd(const float* dy, const float* y, float* g, int64_t n, void* stream);
+/* The same for any TT_ACT_* of tt_conv2d (version 8): g = dy * act'(a) through y = act(a); relu: dy where y > 0, else 0 (torch's
+ * threshold_backward); sigmoid: (dy (1 - y)) y.  dy, y, g 16-byte aligned. */
+int tt_act_bwd(const float* dy, const float* y, float* g, int64_t n, int act, void* stream);
 
 /* Fused ResidualConv2dBlock forward (modules.py:755-777):
  *   y = ELU(W2 . ELU(W1 (*)_dil x + b1) + b2) + x      x,y: (B,C,H,T), W1 (C,C,3,3), W2 (C,C,1,1)
@@ -341,6 +353,20 @@ int tt_convin16_bwd(const float* x, const void* y, const void* dy, const float* 
 int tt_convout16_fwd(const void* x, const float* w, const float* b, float* y, int B, int H, int T, void* stream);
 int tt_convout16_bwd(const void* x, const float* dy, const float* w, void* dx, float* dw, float* db, void* ws, int B, int H,
                      int T, void* stream);
+/* The same four with ONE planar channel (version 8; the magnitude variants, modules.py:892-1075: Encoder.convin = Conv2d(1, 4, 3) + ELU,
+ * Decoder.convout = Conv2d(4, 1, 3) followed by relu (TimbreTrapMag.decode) or sigmoid (TimbreTrapMagDB.decode)):
+ *   tt_convin16_1_fwd   x (B,1,H,T) fp32 -> y cl16 (B,4,H,T); w (4,1,3,3)
+ *   tt_convin16_1_bwd   as tt_convin16_bwd, dx (B,1,H,T) (may be NULL); y == NULL: dy is already gated
+ *   tt_convout16_1_fwd  x cl16 (B,4,H,T) -> y (B,1,H,T) fp32 = act(conv + b), act = TT_ACT_NONE / TT_ACT_RELU / TT_ACT_SIGMOID in the epilogue
+ *   tt_convout16_1_bwd  from x, the saved output y (may be NULL for TT_ACT_NONE) and dy (B,1,H,T): dy is gated by act'(y) inside the kernel
+ *                       (relu: y > 0; sigmoid: (1 - y) y); dx cl16 (written, x S), dw (1,4,3,3), db (1) (+=)
+ * Weight / bias gradients: one partial per workgroup, added in a fixed order (bit-identical from run to run); ws: tt_edge16_scratch_bytes. */
+int tt_convin16_1_fwd(const float* x, const float* w, const float* b, void* y, int B, int H, int T, void* stream);
+int tt_convin16_1_bwd(const float* x, const void* y, const void* dy, const float* w, float* dx, float* dw, float* db, void* ws, int B,
+                      int H, int T, void* stream);
+int tt_convout16_1_fwd(const void* x, const float* w, const float* b, float* y, int B, int H, int T, int act, void* stream);
+int tt_convout16_1_bwd(const void* x, const float* y, const float* dy, const float* w, void* dx, float* dw, float* db, void* ws, int B,
+                       int H, int T, int act, void* stream);
 
 /* EncoderBlock.sconv (modules.py:626-630): y = ELU(Conv2d(C, 2C, (4,1), stride (2,1))(x) + b).
  * x (B,C,H,T) -> y (B,2C,(H-4)/2+1,T); w (2C,C,4,1).  Supported C: 4,8,16,32. */
@@ -437,6 +463,18 @@ int tt_sqdiff2_sum_grad(const float* a1, const float* a2, const float* b, float*
                         float* da1, float* da2, float* db, void* stream);
 int tt_sqdiff_rescale(float* da, float* db, const float* g, int64_t n, void* stream);
 int tt_sqdiff2_rescale(float* da1, float* da2, float* db, const float* g1, const float* g2, int64_t n, void* stream);
+
+/* CQT.to_magnitude (cqtwrapper.py:122-141; version 8): x (outer, 2, inner) -> y (outer, inner) = sqrt(re^2 + im^2). */
+int tt_magnitude(const float* x, float* y, int64_t outer, int64_t inner, void* stream);
+/* CQT.to_decibels (cqtwrapper.py:143-182; version 8), torchaudio AmplitudeToDB('amplitude', top_db=80) per item of dim 0 restated:
+ * for each of `items` items of `per_item` elements, d = 20 log10(max(m, 1e-10)), top = max d over the item, d = max(d, top - 80),
+ * and with `rescale` d = 1 + (d - top) / 80.  Two launches (the item maxima in a fixed order: bit-identical from run to run);
+ * ws: tt_decibels_scratch_bytes(items) bytes of device scratch.  items <= 65535. */
+int64_t tt_decibels_scratch_bytes(int64_t items);
+int tt_decibels(const float* m, float* out, int64_t items, int64_t per_item, int rescale, float* ws, void* stream);
+/* TimbreTrapMag.to_activations (modules.py:994; version 8): act = tanh(c) of n elements, and its backward dc = dact (1 - act^2). */
+int tt_activations1_fwd(const float* coeffs, float* act, int64_t n, void* stream);
+int tt_activations1_bwd(const float* act, const float* dact, float* dcoeffs, int64_t n, void* stream);
 
 /* act = tanh(sqrt(re^2 + im^2)) for coeffs (B,2,F,T) -> (B,F,T) */
 int tt_activations_fwd(const float* coeffs, float* act, int B, int F, int T, void* stream);
@@ -643,6 +681,12 @@ int tt_convin16_bwd_h(const float* x, const void* y, const void* dy, const float
 int tt_convout16_fwd_h(const void* x, const float* w, const float* b, float* y, int B, int H, int T, void* stream);
 int tt_convout16_bwd_h(const void* x, const float* dy, const float* w, void* dx, float* dw, float* db, void* ws, int B, int H,
                      int T, void* stream);
+int tt_convin16_1_fwd_h(const float* x, const float* w, const float* b, void* y, int B, int H, int T, void* stream);
+int tt_convin16_1_bwd_h(const float* x, const void* y, const void* dy, const float* w, float* dx, float* dw, float* db, void* ws, int B,
+                      int H, int T, void* stream);
+int tt_convout16_1_fwd_h(const void* x, const float* w, const float* b, float* y, int B, int H, int T, int act, void* stream);
+int tt_convout16_1_bwd_h(const void* x, const float* y, const float* dy, const float* w, void* dx, float* dw, float* db, void* ws, int B,
+                       int H, int T, int act, void* stream);
 int tt_scaled_add16_h(const void* a, const void* b, const float* s, int idx, void* y, int64_t n, void* stream);
 int tt_dot16_h(const void* a, const void* b, float* out, int64_t n, void* stream);
 int tt_skip_join16_fwd_h(const void* y, const void* e, const float* s, int idx, void* out, int64_t n, int reps, void* stream);

@@ -75,6 +75,21 @@ __device__ __forceinline__ float2 cconj(float2 a) { return make_float2(a.x, -a.y
 // weight from the loss).
 __device__ __forceinline__ float elu1(float a) { return a > 0.f ? a : __expf(a) - 1.f; }
 __device__ __forceinline__ float elu_grad_from_out(float y) { return y > 0.f ? 1.f : y + 1.f; }
+// The output nonlinearities of the magnitude variants' Decoder.convout (reference modules.py:976 relu, :1043 sigmoid), in torch's
+// arithmetic: relu passes a NaN, sigmoid is 1 / (1 + exp(-a)); their derivatives through the saved output y (relu: 1 where y > 0, 0 at
+// 0 like torch's threshold_backward; sigmoid: (1 - y) y, multiplied in torch's order (dy (1 - y)) y).
+__device__ __forceinline__ float act_out(float a, int act) {
+    if (act == TT_ACT_ELU) return elu1(a);
+    if (act == TT_ACT_RELU) return a > 0.f ? a : (a != a ? a : 0.f);
+    if (act == TT_ACT_SIGMOID) return 1.f / (1.f + expf(-a));
+    return a;
+}
+__device__ __forceinline__ float act_grad_from_out(float dy, float y, int act) {
+    if (act == TT_ACT_ELU) return dy * elu_grad_from_out(y);
+    if (act == TT_ACT_RELU) return y > 0.f ? dy : 0.f;
+    if (act == TT_ACT_SIGMOID) return (dy * (1.f - y)) * y;
+    return dy;
+}
 
 // 64-lane wave reductions
 __device__ __forceinline__ float wave_sum(float v) {

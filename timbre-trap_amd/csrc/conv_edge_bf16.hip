@@ -5,6 +5,10 @@
 //   k_cin_bwd    g = dy * ELU'(y) on the fly; dW (4,2,3,3), db; optionally dx (B,2,H,T) fp32 planar (the re-encoded transcription)
 //   k_cout_fwd   cl16 (B,4,H,T) -> logits (B,2,H,T) fp32 planar = conv + b
 //   k_cout_bwd   dy (B,2,H,T) fp32 planar -> dx cl16 (B,4,H,T); dW (2,4,3,3), db
+// The same four with ONE planar channel (the magnitude variants, reference modules.py:892-1075: Encoder.convin Conv2d(1, C0, 3) + ELU,
+// Decoder.convout Conv2d(C0, 1, 3)): the kernels are templated on the planar channel count NP / NO (2 = the entry points above,
+// 1 = the *_1 entry points), and the 1-channel convout takes the variants' output nonlinearity (relu / sigmoid) in its epilogue and
+// gates dy with its derivative through the saved output while staging it (ACT: TT_ACT_NONE / _RELU / _SIGMOID).
 // With 2 x 4 channels there is nothing for the matrix cores: a lane is a pixel, the 72 weights are wave-uniform scalars, the
 // tile (16 rows x 64 frames + 1 halo) sits in LDS as fp32, and the arithmetic is fp32 throughout (only the cl16 tensors
 // are bf16).  Weight / bias gradients: per-lane accumulators over the lane's pixels, reduced over the wave by shuffles and
@@ -53,11 +57,12 @@ __device__ __forceinline__ TileCtx tile_ctx(int v, int tiles_h, int tiles_t, int
 // planes [NP][EROWS][PP] fp32 <- NP consecutive planes of a planar (B,NP,H,T) tensor, zero outside the image.
 // VEC (T % 4 == 0): a thread's element is an aligned float4 of an image row -- 3 loads and 3 sixteen-byte LDS writes per thread and
 // tile instead of 10 + 10 four-byte ones.
-template <int NP, bool VEC>
+// GACT != TT_ACT_NONE: each element is stored as dy * act'(y) with y the saved output at the same place (both zero outside the image)
+template <int NP, bool VEC, int GACT = TT_ACT_NONE>
 struct StagePlanar {
     static constexpr int PER_ROW = VEC ? PP / 4 : ERW, NEL = NP * EROWS * PER_ROW, NIT = (NEL + NT - 1) / NT;
     typedef typename std::conditional<VEC, f32x4, float>::type V;
-    V v[NIT];
+    V v[NIT], yv[GACT != TT_ACT_NONE ? NIT : 1];
     unsigned rel[NIT];                                           // byte offset of element `it` from the tile's first staged element
     static __device__ __forceinline__ void where(int i, int& pl, int& row, int& col) {      // col: frame - t0
         pl = i / (EROWS * PER_ROW);
@@ -73,12 +78,18 @@ struct StagePlanar {
             rel[it] = it * NT + tid < NEL ? (unsigned)((pl * H + row) * T + col + (VEC ? 4 : 1)) * 4u : 0u;
         }
     }
-    __device__ __forceinline__ void load(const float* src, const TileCtx& c, int H, int T, int tid) {
+    __device__ __forceinline__ void load(const float* src, const TileCtx& c, int H, int T, int tid, const float* ysrc = nullptr) {
         const ETile tl = c.tl;
         if (VEC ? c.interior_v : c.interior) {
-            const char* base = reinterpret_cast<const char*>(src + ((long)tl.b * NP * H + (tl.h0 - 1)) * T + (tl.t0 - (VEC ? 4 : 1)));
+            const long first = ((long)tl.b * NP * H + (tl.h0 - 1)) * T + (tl.t0 - (VEC ? 4 : 1));
+            const char* base = reinterpret_cast<const char*>(src + first);
 #pragma unroll
             for (int it = 0; it < NIT; ++it) v[it] = *reinterpret_cast<const V*>(base + rel[it]);
+            if constexpr (GACT != TT_ACT_NONE) {
+                const char* ybase = reinterpret_cast<const char*>(ysrc + first);
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) yv[it] = *reinterpret_cast<const V*>(ybase + rel[it]);
+            }
             return;
         }
 #pragma unroll
@@ -87,8 +98,13 @@ struct StagePlanar {
             where(it * NT + tid, pl, row, col);
             const int h = tl.h0 - 1 + row, t = tl.t0 + col;      // VEC: T % 4 == 0 and t % 4 == 0, so the four frames are in or out together
             const bool ok = it * NT + tid < NEL && (unsigned)h < (unsigned)H && (unsigned)t < (unsigned)T;
-            const V q = *reinterpret_cast<const V*>(src + (ok ? (((long)tl.b * NP + pl) * H + h) * T + t : 0));
+            const long off = ok ? (((long)tl.b * NP + pl) * H + h) * T + t : 0;
+            const V q = *reinterpret_cast<const V*>(src + off);
             if constexpr (VEC) { v[it] = ok ? q : V{0.f, 0.f, 0.f, 0.f}; } else { v[it] = ok ? q : 0.f; }
+            if constexpr (GACT != TT_ACT_NONE) {
+                const V qy = *reinterpret_cast<const V*>(ysrc + off);
+                if constexpr (VEC) { yv[it] = ok ? qy : V{0.f, 0.f, 0.f, 0.f}; } else { yv[it] = ok ? qy : 0.f; }
+            }
         }
     }
     __device__ __forceinline__ void store(float* lds, int tid) const {
@@ -97,7 +113,16 @@ struct StagePlanar {
             if (it * NT + tid >= NEL) continue;
             int pl, row, col;
             where(it * NT + tid, pl, row, col);
-            *reinterpret_cast<V*>(lds + pl * PPLANE + row * PP + col + 4) = v[it];
+            V e = v[it];
+            if constexpr (GACT != TT_ACT_NONE) {
+                if constexpr (VEC) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) e[j] = act_grad_from_out(e[j], yv[it][j], GACT);
+                } else {
+                    e = act_grad_from_out(e, yv[it], GACT);
+                }
+            }
+            *reinterpret_cast<V*>(lds + pl * PPLANE + row * PP + col + 4) = e;
         }
     }
 };
@@ -263,6 +288,10 @@ struct PWin {
         w[2].load(lds, (r + 2) * ERW + lane);
     }
     template <int K, int C> __device__ __forceinline__ f32x2 tap() const { return w[K / 3].template tap<K % 3, C>(); }
+    // channels (2P, 2P + 1) of tap K: the operand pairs of the one-output-channel convolution
+    template <int K, int P> __device__ __forceinline__ f32x2 pair() const {
+        return __builtin_shufflevector(w[K / 3].px[K % 3], w[K / 3].px[K % 3], 2 * P, 2 * P + 1);
+    }
 };
 // compile-time loops: f(integral_constant)
 template <int K, class F> __device__ __forceinline__ void taps9(F&& f) {
@@ -273,16 +302,16 @@ template <int I, int N, class F> __device__ __forceinline__ void static_for(F&& 
 }
 
 // ---- Encoder.convin ------------------------------------------------------------------------------------------------------------
-template <bool VEC>
+template <bool VEC, int NP = 2>
 __global__ __launch_bounds__(NT) void k_cin_fwd(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                                                  e16* __restrict__ y, int H, int T, int tiles_h, int tiles_t, int ntiles) {
-    __shared__ __attribute__((aligned(16))) float xs[2 * PPLANE];
+    __shared__ __attribute__((aligned(16))) float xs[NP * PPLANE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float wa[18];                                                // [ci * 9 + k]: w[co = lane % 4][ci][k], the A operand of the 4x4x1 products
+    float wa[NP * 9];                                            // [ci * 9 + k]: w[co = lane % 4][ci][k], the A operand of the 4x4x1 products
 #pragma unroll
-    for (int i = 0; i < 18; ++i) wa[i] = w[(lane & 3) * 18 + i];
+    for (int i = 0; i < NP * 9; ++i) wa[i] = w[(lane & 3) * NP * 9 + i];
     const f32x4 br = {bias[0], bias[1], bias[2], bias[3]};
-    StagePlanar<2, VEC> sx;
+    StagePlanar<NP, VEC> sx;
     sx.init(H, T, tid);
     if (blockIdx.x < ntiles) sx.load(x, tile_ctx(blockIdx.x, tiles_h, tiles_t, ntiles, H, T), H, T, tid);
     for (int v = blockIdx.x; v < ntiles; v += gridDim.x) {
@@ -292,7 +321,7 @@ __global__ __launch_bounds__(NT) void k_cin_fwd(const float* __restrict__ x, con
         __syncthreads();
         if (v + gridDim.x < ntiles) sx.load(x, tile_ctx(v + gridDim.x, tiles_h, tiles_t, ntiles, H, T), H, T, tid);
         const int t = tl.t0 + lane, r0 = wave * ERPW;
-        Win<2> xw;
+        Win<NP> xw;
         xw.start(xs, r0, lane);
         e16x4 o[ERPW];                                          // stores after the rows: no branch between them (one basic block, so
 #pragma unroll                                                   // that every tap broadcast folds into the multiply-add's op_sel)
@@ -302,9 +331,9 @@ __global__ __launch_bounds__(NT) void k_cin_fwd(const float* __restrict__ x, con
             taps9<0>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
                 a0 = mfma441(wa[k], xw.template one<k>(0), a0);
-                a1 = mfma441(wa[9 + k], xw.template one<k>(1), a1);
+                if constexpr (NP == 2) a1 = mfma441(wa[9 + k], xw.template one<k>(1), a1);
             });
-            const f32x4 a = a0 + a1;
+            const f32x4 a = NP == 2 ? a0 + a1 : a0;
             o[rr][0] = (e16)elu_f(a[0]); o[rr][1] = (e16)elu_f(a[1]);
             o[rr][2] = (e16)elu_f(a[2]); o[rr][3] = (e16)elu_f(a[3]);
             asm volatile("" :: "v"(o[rr]));
@@ -321,27 +350,28 @@ __global__ __launch_bounds__(NT) void k_cin_fwd(const float* __restrict__ x, con
 // dW[co][ci][k] = sum g[co][p] x[ci][p + k];  db[co] = sum g[co];  dx[ci][p] = sum_{co,k} W[co][ci][k] g[co][p - k]
 // (g and x are zero outside the image in LDS, so only the stores are masked)
 // PRE: dy arrives already gated (the first level's backward left dy * ELU'(y): tt_wide_level_bwd_gated) -- y is not read
-template <bool DX, bool VEC, bool PRE = false>
+template <bool DX, bool VEC, bool PRE = false, int NP = 2>
 __global__ __launch_bounds__(NT, 2) void k_cin_bwd(const float* __restrict__ x, const e16* __restrict__ y, const e16* __restrict__ dy,
                                                  const float* __restrict__ w, float* __restrict__ dx, float* __restrict__ part,
                                                  int H, int T, int tiles_h, int tiles_t, int ntiles, float unscale) {
-    __shared__ __attribute__((aligned(16))) float xs[2 * PPLANE];
+    constexpr int NW = NP * 36;                                  // weight partials; then the 4 bias sums
+    __shared__ __attribute__((aligned(16))) float xs[NP * PPLANE];
     __shared__ __attribute__((aligned(16))) float gs[4 * EPLANE + 4];
-    __shared__ float red[4 * 76];
-    __shared__ __attribute__((aligned(16))) float wl[72];       // [(co * 9 + k) * 2 + ci]
+    __shared__ float red[4 * (NW + 4)];
+    __shared__ __attribute__((aligned(16))) float wl[NW];       // [(co * 9 + k) * NP + ci]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // dy carries the calling thread's loss scale S (a power of two): the fp32 data gradient leaves the scaled region through weights
     // multiplied by 1 / S (exact), the weight / bias sums through k_edge_reduce
-    if (DX && tid < 72) { const int ci = tid & 1, q = tid >> 1; wl[tid] = unscale * w[((q / 9) * 2 + ci) * 9 + q % 9]; }
-    f32x2 acc[2][18];                                            // [co pair][ci * 9 + k]: dW of co = 2p (lane 0) and 2p + 1 (lane 1)
+    if (DX && tid < NW) { const int ci = tid % NP, q = tid / NP; wl[tid] = unscale * w[((q / 9) * NP + ci) * 9 + q % 9]; }
+    f32x2 acc[2][NP * 9];                                        // [co pair][ci * 9 + k]: dW of co = 2p (lane 0) and 2p + 1 (lane 1)
     f32x2 accb[2];
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
 #pragma unroll
-        for (int i = 0; i < 18; ++i) acc[p][i] = splat2(0.f);
+        for (int i = 0; i < NP * 9; ++i) acc[p][i] = splat2(0.f);
         accb[p] = splat2(0.f);
     }
-    StagePlanar<2, VEC> sx;
+    StagePlanar<NP, VEC> sx;
     StageCl4<!PRE> sg;
     sx.init(H, T, tid); sg.init(T, tid);
     if (blockIdx.x < ntiles) {
@@ -360,7 +390,7 @@ __global__ __launch_bounds__(NT, 2) void k_cin_bwd(const float* __restrict__ x, 
         }
         const int t = tl.t0 + lane, r0 = wave * ERPW;
         {
-            Win<2> xw;
+            Win<NP> xw;
             xw.start(xs, r0, lane);
 #pragma unroll
             for (int rr = 0; rr < ERPW; ++rr) {
@@ -370,7 +400,7 @@ __global__ __launch_bounds__(NT, 2) void k_cin_bwd(const float* __restrict__ x, 
                 f32x2 g[2] = {__builtin_shufflevector(gc, gc, 0, 1), __builtin_shufflevector(gc, gc, 2, 3)};
                 accb[0] += g[0]; accb[1] += g[1];
 #pragma unroll
-                for (int ci = 0; ci < 2; ++ci)
+                for (int ci = 0; ci < NP; ++ci)
                     taps9<0>([&](auto kc) {
                         constexpr int k = decltype(kc)::value;
                         const f32x2 xv = xw.template tap<k>(ci);
@@ -381,7 +411,32 @@ __global__ __launch_bounds__(NT, 2) void k_cin_bwd(const float* __restrict__ x, 
                 row_fence();
             }
         }
-        if constexpr (DX) {
+        if constexpr (DX && NP == 1) {                           // one input channel: the same sums on scalars
+            float d[ERPW];
+#pragma unroll
+            for (int rr = 0; rr < ERPW; ++rr) d[rr] = 0.f;
+            static_for<0, 3>([&](auto jc) {
+                constexpr int j = decltype(jc)::value;
+                f32x4 gw[ERPW + 2];
+#pragma unroll
+                for (int i = 0; i < ERPW + 2; ++i) gw[i] = *reinterpret_cast<const f32x4*>(gs + ((r0 + i) * ERW + lane + j) * 4);
+                static_for<0, 12>([&](auto qc) {
+                    constexpr int co = decltype(qc)::value / 3, kh = decltype(qc)::value % 3, k = kh * 3 + (2 - j);
+                    const float w1 = wl[co * 9 + k];
+#pragma unroll
+                    for (int rr = 0; rr < ERPW; ++rr) d[rr] = __builtin_fmaf(w1, gw[rr + 2 - kh][co], d[rr]);
+                });
+#pragma unroll
+                for (int rr = 0; rr < ERPW; ++rr) asm volatile("" : "+v"(d[rr]));
+                row_fence();
+            });
+#pragma unroll
+            for (int rr = 0; rr < ERPW; ++rr) {
+                const int h = tl.h0 + r0 + rr;
+                if (t < T && h < H) dx[((long)tl.b * H + h) * T + t] = d[rr];
+            }
+        }
+        if constexpr (DX && NP == 2) {
             f32x2 d[ERPW];                                       // (ci 0, ci 1) of the wave's rows
 #pragma unroll
             for (int rr = 0; rr < ERPW; ++rr) d[rr] = splat2(0.f);
@@ -411,26 +466,34 @@ __global__ __launch_bounds__(NT, 2) void k_cin_bwd(const float* __restrict__ x, 
         }
     }
     __syncthreads();
-    float flat[76];                                              // back to [co][ci][k], then the 4 bias sums
+    float flat[NW + 4];                                          // back to [co][ci][k], then the 4 bias sums
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
 #pragma unroll
-        for (int i = 0; i < 18; ++i) { flat[(2 * p) * 18 + i] = acc[p][i][0]; flat[(2 * p + 1) * 18 + i] = acc[p][i][1]; }
-        flat[72 + 2 * p] = accb[p][0]; flat[72 + 2 * p + 1] = accb[p][1];
+        for (int i = 0; i < NP * 9; ++i) { flat[(2 * p) * NP * 9 + i] = acc[p][i][0]; flat[(2 * p + 1) * NP * 9 + i] = acc[p][i][1]; }
+        flat[NW + 2 * p] = accb[p][0]; flat[NW + 2 * p + 1] = accb[p][1];
     }
-    const float tot = wg_total<76>(flat, red, tid);
-    if (tid < 76) part[(long)blockIdx.x * NPARTW + tid] = tot;
+    const float tot = wg_total<NW + 4>(flat, red, tid);
+    if (tid < NW + 4) part[(long)blockIdx.x * NPARTW + tid] = tot;
 }
 
 // ---- Decoder.convout -----------------------------------------------------------------------------------------------------------
+// NO = 1: one output channel, the four input channels as two register pairs (ci 0, 1) and (ci 2, 3); ACT fused into the epilogue
+template <int NO = 2, int ACT = TT_ACT_NONE>
 __global__ __launch_bounds__(NT) void k_cout_fwd(const e16* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                                                   float* __restrict__ y, int H, int T, int tiles_h, int tiles_t, int ntiles) {
     __shared__ __attribute__((aligned(16))) float xs[4 * EPLANE + 4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    f32x2 wr[36], br;                                            // [ci * 9 + k] = (w[0][ci][k], w[1][ci][k])
+    f32x2 wr[NO == 2 ? 36 : 18], br;                             // NO 2: [ci * 9 + k] = (w[0][ci][k], w[1][ci][k]); NO 1: [p * 9 + k] = (w[0][2p][k], w[0][2p + 1][k])
+    if constexpr (NO == 2) {
 #pragma unroll
-    for (int i = 0; i < 36; ++i) { wr[i][0] = w[i]; wr[i][1] = w[36 + i]; asm volatile("" : "+v"(wr[i])); }
-    br[0] = bias[0]; br[1] = bias[1];
+        for (int i = 0; i < 36; ++i) { wr[i][0] = w[i]; wr[i][1] = w[36 + i]; asm volatile("" : "+v"(wr[i])); }
+        br[0] = bias[0]; br[1] = bias[1];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 18; ++i) { wr[i][0] = w[(2 * (i / 9)) * 9 + i % 9]; wr[i][1] = w[(2 * (i / 9) + 1) * 9 + i % 9]; asm volatile("" : "+v"(wr[i])); }
+        br[0] = bias[0]; br[1] = 0.f;
+    }
     StageCl4<false> sx;
     sx.init(T, tid);
     if (blockIdx.x < ntiles) sx.load(x, nullptr, tile_ctx(blockIdx.x, tiles_h, tiles_t, ntiles, H, T), H, T, tid);
@@ -447,8 +510,12 @@ __global__ __launch_bounds__(NT) void k_cout_fwd(const e16* __restrict__ x, cons
         for (int rr = 0; rr < ERPW; ++rr) {
             const int h = tp.h0 + r0 + rr;
             if (t < T && h < H) {
-                y[(((long)tp.b * 2 + 0) * H + h) * T + t] = o[rr][0];
-                y[(((long)tp.b * 2 + 1) * H + h) * T + t] = o[rr][1];
+                if constexpr (NO == 2) {
+                    y[(((long)tp.b * 2 + 0) * H + h) * T + t] = o[rr][0];
+                    y[(((long)tp.b * 2 + 1) * H + h) * T + t] = o[rr][1];
+                } else {
+                    y[((long)tp.b * H + h) * T + t] = o[rr][0];
+                }
             }
         }
     };
@@ -464,12 +531,23 @@ __global__ __launch_bounds__(NT) void k_cout_fwd(const e16* __restrict__ x, cons
 #pragma unroll
         for (int rr = 0; rr < ERPW; ++rr) {
             xw.advance(xs, r0 + rr, lane);
-            f32x2 a4[4] = {br, splat2(0.f), splat2(0.f), splat2(0.f)};          // one chain per input channel
-            static_for<0, 36>([&](auto ic) {
-                constexpr int ci = decltype(ic)::value / 9, k = decltype(ic)::value % 9;
-                a4[ci] = wr[ci * 9 + k] * xw.template tap<k, ci>() + a4[ci];
-            });
-            o[rr] = (a4[0] + a4[1]) + (a4[2] + a4[3]);
+            if constexpr (NO == 2) {
+                f32x2 a4[4] = {br, splat2(0.f), splat2(0.f), splat2(0.f)};          // one chain per input channel
+                static_for<0, 36>([&](auto ic) {
+                    constexpr int ci = decltype(ic)::value / 9, k = decltype(ic)::value % 9;
+                    a4[ci] = wr[ci * 9 + k] * xw.template tap<k, ci>() + a4[ci];
+                });
+                o[rr] = (a4[0] + a4[1]) + (a4[2] + a4[3]);
+            } else {
+                f32x2 a2[2] = {br, splat2(0.f)};                 // chains over the input-channel pairs (0, 1) and (2, 3)
+                static_for<0, 18>([&](auto ic) {
+                    constexpr int p = decltype(ic)::value / 9, k = decltype(ic)::value % 9;
+                    a2[p] = wr[p * 9 + k] * xw.template pair<k, p>() + a2[p];
+                });
+                const f32x2 a = a2[0] + a2[1];
+                o[rr][0] = act_out(a[0] + a[1], ACT);
+                o[rr][1] = 0.f;
+            }
             asm volatile("" : "+v"(o[rr]));
             row_fence();
         }
@@ -478,26 +556,28 @@ __global__ __launch_bounds__(NT) void k_cout_fwd(const e16* __restrict__ x, cons
     flush();
 }
 
-template <bool VEC>
+// NO = 1: dy (B,1,H,T), staged as dy * act'(y) from the saved output y (ACT); dW (1,4,3,3) accumulated on the input-channel pairs
+template <bool VEC, int NO = 2, int ACT = TT_ACT_NONE>
 __global__ __launch_bounds__(NT, 2) void k_cout_bwd(const e16* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ w,
                                                   e16* __restrict__ dx, float* __restrict__ part, int H, int T, int tiles_h,
-                                                  int tiles_t, int ntiles, float scale) {
+                                                  int tiles_t, int ntiles, float scale, const float* __restrict__ ysaved = nullptr) {
+    constexpr int NW = NO * 36;
     __shared__ __attribute__((aligned(16))) float xs[4 * EPLANE + 4];
-    __shared__ __attribute__((aligned(16))) float gs[2 * PPLANE];
-    __shared__ float red[4 * 74];
+    __shared__ __attribute__((aligned(16))) float gs[NO * PPLANE];
+    __shared__ float red[4 * (NW + NO)];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float wa[18];                                                // [co * 9 + k]: w[co][ci = lane % 4][k], the A operand of the data gradient
+    float wa[NO * 9];                                            // [co * 9 + k]: w[co][ci = lane % 4][k], the A operand of the data gradient
 #pragma unroll
-    for (int i = 0; i < 18; ++i) wa[i] = scale * w[((i / 9) * 4 + (lane & 3)) * 9 + i % 9];    // dx ENTERS the loss-scaled 16-bit region: x S (exact)
-    f32x2 acc[36], accb = splat2(0.f);                           // [ci * 9 + k]: dW of co 0 (lane 0) and co 1 (lane 1)
+    for (int i = 0; i < NO * 9; ++i) wa[i] = scale * w[((i / 9) * 4 + (lane & 3)) * 9 + i % 9];    // dx ENTERS the loss-scaled 16-bit region: x S (exact)
+    f32x2 acc[NO == 2 ? 36 : 18], accb = splat2(0.f);            // NO 2: [ci * 9 + k] = dW of co 0 (lane 0) and co 1 (lane 1); NO 1: [p * 9 + k] = ci 2p, 2p + 1
 #pragma unroll
-    for (int i = 0; i < 36; ++i) acc[i] = splat2(0.f);
+    for (int i = 0; i < (NO == 2 ? 36 : 18); ++i) acc[i] = splat2(0.f);
     StageCl4<false> sx;
-    StagePlanar<2, VEC> sg;
+    StagePlanar<NO, VEC, NO == 2 ? TT_ACT_NONE : ACT> sg;
     sx.init(T, tid); sg.init(H, T, tid);
     if (blockIdx.x < ntiles) {
         const TileCtx t0 = tile_ctx(blockIdx.x, tiles_h, tiles_t, ntiles, H, T);
-        sx.load(x, nullptr, t0, H, T, tid); sg.load(dy, t0, H, T, tid);
+        sx.load(x, nullptr, t0, H, T, tid); sg.load(dy, t0, H, T, tid, ysaved);
     }
     for (int v = blockIdx.x; v < ntiles; v += gridDim.x) {
         const ETile tl = etile(v, tiles_h, tiles_t, ntiles);
@@ -507,7 +587,7 @@ __global__ __launch_bounds__(NT, 2) void k_cout_bwd(const e16* __restrict__ x, c
         __syncthreads();
         if (v + gridDim.x < ntiles) {
             const TileCtx tn = tile_ctx(v + gridDim.x, tiles_h, tiles_t, ntiles, H, T);
-            sx.load(x, nullptr, tn, H, T, tid); sg.load(dy, tn, H, T, tid);
+            sx.load(x, nullptr, tn, H, T, tid); sg.load(dy, tn, H, T, tid, ysaved);
         }
         const int t = tl.t0 + lane, r0 = wave * ERPW;
         {                                                        // weight gradient on the vector ALUs: 36 packed multiply-adds per row
@@ -518,12 +598,21 @@ __global__ __launch_bounds__(NT, 2) void k_cout_bwd(const e16* __restrict__ x, c
                 const int r = r0 + rr, ctr = (r + 1) * PP + lane + PCOL0 + 1;
                 xw.advance(xs, r, lane);
                 f32x2 g;
-                g[0] = gs[ctr]; g[1] = gs[PPLANE + ctr];
-                accb += g;
-                static_for<0, 36>([&](auto ic) {
-                    constexpr int i = decltype(ic)::value;
-                    acc[i] = g * xw.template tap<i % 9, i / 9>() + acc[i];
-                });
+                if constexpr (NO == 2) {
+                    g[0] = gs[ctr]; g[1] = gs[PPLANE + ctr];
+                    accb += g;
+                    static_for<0, 36>([&](auto ic) {
+                        constexpr int i = decltype(ic)::value;
+                        acc[i] = g * xw.template tap<i % 9, i / 9>() + acc[i];
+                    });
+                } else {
+                    g = splat2(gs[ctr]);
+                    accb[0] += g[0];
+                    static_for<0, 18>([&](auto ic) {
+                        constexpr int i = decltype(ic)::value;
+                        acc[i] = g * xw.template pair<i % 9, i / 9>() + acc[i];
+                    });
+                }
                 pin(acc); asm volatile("" : "+v"(accb));
                 row_fence();
             }
@@ -534,7 +623,7 @@ __global__ __launch_bounds__(NT, 2) void k_cout_bwd(const e16* __restrict__ x, c
 #pragma unroll
         for (int rr = 0; rr < ERPW; ++rr) d[rr] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int co = 0; co < 2; ++co) {
+        for (int co = 0; co < NO; ++co) {
             WRow<1> gw[ERPW + 2];                                // halo rows r0 .. r0 + ERPW + 1 of dy[co]
 #pragma unroll
             for (int i = 0; i < ERPW + 2; ++i) gw[i].load(gs + co * PPLANE, (r0 + i) * PP + lane + PCOL0);
@@ -554,30 +643,37 @@ __global__ __launch_bounds__(NT, 2) void k_cout_bwd(const e16* __restrict__ x, c
         }
     }
     __syncthreads();
-    float flat[74];
+    float flat[NW + NO];
+    if constexpr (NO == 2) {
 #pragma unroll
-    for (int i = 0; i < 36; ++i) { flat[i] = acc[i][0]; flat[36 + i] = acc[i][1]; }
-    flat[72] = accb[0]; flat[73] = accb[1];
-    const float tot = wg_total<74>(flat, red, tid);
-    if (tid < 74) part[(long)blockIdx.x * NPARTW + tid] = tot;
+        for (int i = 0; i < 36; ++i) { flat[i] = acc[i][0]; flat[36 + i] = acc[i][1]; }
+        flat[72] = accb[0]; flat[73] = accb[1];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 18; ++i) { flat[(2 * (i / 9)) * 9 + i % 9] = acc[i][0]; flat[(2 * (i / 9) + 1) * 9 + i % 9] = acc[i][1]; }
+        flat[36] = accb[0];
+    }
+    const float tot = wg_total<NW + NO>(flat, red, tid);
+    if (tid < NW + NO) part[(long)blockIdx.x * NPARTW + tid] = tot;
 }
 
-// dw[e] += sum over workgroups (e < 72), db[e - 72] likewise; 1024 threads = 64 elements x 16 slices
+// dw[e] += sum over workgroups (e < nw: 72, or 36 for the one-channel edges), db[e - nw] likewise; 1024 threads = 64 elements x 16
+// slices, each slice summing its workgroups in ascending order and the slices added in a fixed order: bit-identical from run to run
 __global__ __launch_bounds__(1024) void k_edge_reduce(const float* __restrict__ part, int nwg, float* __restrict__ dw, float* __restrict__ db,
-                                                       int nb, float scale) {
+                                                       int nb, float scale, int nw = 72) {
     __shared__ float red[16][64];
     const int el = threadIdx.x & 63, sl = threadIdx.x >> 6;
     const int e = blockIdx.x * 64 + el;
     float s = 0.f;
-    if (e < 72 + nb)
+    if (e < nw + nb)
         for (int j = sl; j < nwg; j += 16) s += part[(long)j * NPARTW + e];
     red[sl][el] = s;
     __syncthreads();
-    if (sl != 0 || e >= 72 + nb) return;
+    if (sl != 0 || e >= nw + nb) return;
     float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < 16; ++i) sum += red[i][el];
-    if (e < 72) dw[e] += sum * scale; else db[e - 72] += sum * scale;
+    if (e < nw) dw[e] += sum * scale; else db[e - nw] += sum * scale;
 }
 
 constexpr int EDGE_MAX_WG = 1024;
@@ -641,6 +737,72 @@ int tt_convout16_bwd(const void* x, const float* dy, const float* w, void* dx, f
     else hipLaunchKernelGGL(k_cout_bwd<false>, dim3(grid), dim3(NT), 0, st, (const e16*)x, dy, w, (e16*)dx, (float*)ws, H, T, th, tt, n, tt_loss_scale());
     TT_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_edge_reduce, dim3(2), dim3(1024), 0, st, (const float*)ws, grid, dw, db, 2, 1.f);   // dW, db from the fp32 dy itself
+    TT_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- the one-channel edges of the magnitude variants (version 8) ----------------------------------------------------------------
+int tt_convin16_1_fwd(const float* x, const float* w, const float* b, void* y, int B, int H, int T, void* stream) {
+    if (!x || !w || !b || !y || !edge_ok(B, H, T)) return TT_E_BADARG;
+    int th, tt, n; edge_tiles(B, H, T, th, tt, n);
+    if (T % 4 == 0) hipLaunchKernelGGL((k_cin_fwd<true, 1>), dim3(edge_grid(n)), dim3(NT), 0, tt_stream(stream), x, w, b, (e16*)y, H, T, th, tt, n);
+    else hipLaunchKernelGGL((k_cin_fwd<false, 1>), dim3(edge_grid(n)), dim3(NT), 0, tt_stream(stream), x, w, b, (e16*)y, H, T, th, tt, n);
+    TT_LAUNCH_CHECK();
+    return 0;
+}
+
+int tt_convin16_1_bwd(const float* x, const void* y, const void* dy, const float* w, float* dx, float* dw, float* db, void* ws, int B,
+                      int H, int T, void* stream) {
+    if (!x || !dy || !w || !dw || !db || !ws || !edge_ok(B, H, T)) return TT_E_BADARG;       // y == NULL: dy is already gated
+    int th, tt, n; edge_tiles(B, H, T, th, tt, n);
+    const int grid = edge_grid(n);
+    hipStream_t st = tt_stream(stream);
+    const bool vec = T % 4 == 0;
+#define CIN1_BWD(DX_, V_, P_) hipLaunchKernelGGL((k_cin_bwd<DX_, V_, P_, 1>), dim3(grid), dim3(NT), 0, st, x, (const e16*)y, (const e16*)dy, w, dx, (float*)ws, H, T, th, tt, n, tt_loss_unscale())
+    if (y) {
+        if (dx) { if (vec) CIN1_BWD(true, true, false); else CIN1_BWD(true, false, false); }
+        else { if (vec) CIN1_BWD(false, true, false); else CIN1_BWD(false, false, false); }
+    } else {
+        if (dx) { if (vec) CIN1_BWD(true, true, true); else CIN1_BWD(true, false, true); }
+        else { if (vec) CIN1_BWD(false, true, true); else CIN1_BWD(false, false, true); }
+    }
+#undef CIN1_BWD
+    TT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_edge_reduce, dim3(1), dim3(1024), 0, st, (const float*)ws, grid, dw, db, 4, tt_loss_unscale(), 36);
+    TT_LAUNCH_CHECK();
+    return 0;
+}
+
+int tt_convout16_1_fwd(const void* x, const float* w, const float* b, float* y, int B, int H, int T, int act, void* stream) {
+    if (!x || !w || !b || !y || !edge_ok(B, H, T)) return TT_E_BADARG;
+    int th, tt, n; edge_tiles(B, H, T, th, tt, n);
+    hipStream_t st = tt_stream(stream);
+    const dim3 grid(edge_grid(n));
+    if (act == TT_ACT_NONE) hipLaunchKernelGGL((k_cout_fwd<1, TT_ACT_NONE>), grid, dim3(NT), 0, st, (const e16*)x, w, b, y, H, T, th, tt, n);
+    else if (act == TT_ACT_RELU) hipLaunchKernelGGL((k_cout_fwd<1, TT_ACT_RELU>), grid, dim3(NT), 0, st, (const e16*)x, w, b, y, H, T, th, tt, n);
+    else if (act == TT_ACT_SIGMOID) hipLaunchKernelGGL((k_cout_fwd<1, TT_ACT_SIGMOID>), grid, dim3(NT), 0, st, (const e16*)x, w, b, y, H, T, th, tt, n);
+    else return TT_E_BADARG;
+    TT_LAUNCH_CHECK();
+    return 0;
+}
+
+int tt_convout16_1_bwd(const void* x, const float* y, const float* dy, const float* w, void* dx, float* dw, float* db, void* ws, int B, int H,
+                       int T, int act, void* stream) {
+    if (!x || !dy || !w || !dx || !dw || !db || !ws || !edge_ok(B, H, T)) return TT_E_BADARG;
+    if ((act != TT_ACT_NONE && act != TT_ACT_RELU && act != TT_ACT_SIGMOID) || (act != TT_ACT_NONE && !y)) return TT_E_BADARG;
+    int th, tt, n; edge_tiles(B, H, T, th, tt, n);
+    const int grid = edge_grid(n);
+    hipStream_t st = tt_stream(stream);
+    const float s = tt_loss_scale();
+#define COUT1_BWD(V_, A_) hipLaunchKernelGGL((k_cout_bwd<V_, 1, A_>), dim3(grid), dim3(NT), 0, st, (const e16*)x, dy, w, (e16*)dx, (float*)ws, H, T, th, tt, n, s, y)
+    if (T % 4 == 0) {
+        if (act == TT_ACT_NONE) COUT1_BWD(true, TT_ACT_NONE); else if (act == TT_ACT_RELU) COUT1_BWD(true, TT_ACT_RELU); else COUT1_BWD(true, TT_ACT_SIGMOID);
+    } else {
+        if (act == TT_ACT_NONE) COUT1_BWD(false, TT_ACT_NONE); else if (act == TT_ACT_RELU) COUT1_BWD(false, TT_ACT_RELU); else COUT1_BWD(false, TT_ACT_SIGMOID);
+    }
+#undef COUT1_BWD
+    TT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_edge_reduce, dim3(1), dim3(1024), 0, st, (const float*)ws, grid, dw, db, 1, 1.f, 36);   // dW, db from the fp32 dy itself
     TT_LAUNCH_CHECK();
     return 0;
 }

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) void k_conv_generic(ConvP p) {
             for (int c = 0; c < CO_T; ++c) {
                 if (co0 + c >= p.Cout) break;
                 float v = acc[c];
-                if (p.act == TT_ACT_ELU) v = elu1(v);
+                v = act_out(v, p.act);
                 const long o = ((long)b * p.Cout + co0 + c) * yplane + (long)ho * p.T + t;
                 if (p.res) v += p.res[o];
                 p.y[o] = v;
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256) void k_conv3x3_small(ConvP p) {
 #pragma unroll
         for (int co = 0; co < COUT; ++co) {
             float v = acc[co];
-            if (p.act == TT_ACT_ELU) v = elu1(v);
+            v = act_out(v, p.act);
             if (p.res) v += p.res[o + co * plane];
             p.y[o + co * plane] = v;
         }
@@ -485,7 +485,7 @@ __global__ __launch_bounds__(512) void k_conv3x3_lds(ConvP p) {
 #pragma unroll
                 for (int co = 0; co < CO; ++co) {
                     float val = acc[r][co];
-                    if (p.act == TT_ACT_ELU) val = elu1(val);
+                    val = act_out(val, p.act);
                     if (p.res) val += p.res[o + co * plane];
                     p.y[o + co * plane] = val;
                 }
@@ -533,7 +533,7 @@ extern "C" int tt_conv2d(const float* x, const float* w, const float* bias, cons
     ConvP p{x, w, bias, res, y, B, Cin, Hin, T, Cout, Hout, KH, KW, stride_h, dil_h, dil_w, pad_h, pad_w,
             transposed, (long)ws_co, (long)ws_ci, (long)ws_kh, (long)ws_kw, act};
     if (KH == 3 && KW == 3 && stride_h == 1 && dil_h == 1 && dil_w == 1 && pad_h == 1 && pad_w == 1 && !transposed &&
-        Hin == Hout && (Cin == 2 || Cin == 4) && (Cout == 2 || Cout == 4)) {
+        Hin == Hout && (Cin == 1 || Cin == 2 || Cin == 4) && (Cout == 1 || Cout == 2 || Cout == 4) && Cin * Cout > 1) {
         if (T % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (long)Cin * Hin * T < (1L << 31) && (long)Cout * Hin * T < (1L << 31)) {
             if (Cin == 2 && Cout == 4) return launch_conv3x3_lds<2, 4>(p, tt_stream(stream));
             if (Cin == 4 && Cout == 2) return launch_conv3x3_lds<4, 2>(p, tt_stream(stream));
@@ -542,7 +542,13 @@ extern "C" int tt_conv2d(const float* x, const float* w, const float* bias, cons
         if (Cin == 2 && Cout == 4) hipLaunchKernelGGL((k_conv3x3_small<2, 4>), g3, dim3(256), 0, tt_stream(stream), p);
         else if (Cin == 4 && Cout == 2) hipLaunchKernelGGL((k_conv3x3_small<4, 2>), g3, dim3(256), 0, tt_stream(stream), p);
         else if (Cin == 2 && Cout == 2) hipLaunchKernelGGL((k_conv3x3_small<2, 2>), g3, dim3(256), 0, tt_stream(stream), p);
-        else hipLaunchKernelGGL((k_conv3x3_small<4, 4>), g3, dim3(256), 0, tt_stream(stream), p);
+        // the 1-channel edges of the magnitude variants (Encoder.convin 1 -> C0, Decoder.convout C0 -> 1) and their data gradients
+        else if (Cin == 1 && Cout == 4) hipLaunchKernelGGL((k_conv3x3_small<1, 4>), g3, dim3(256), 0, tt_stream(stream), p);
+        else if (Cin == 4 && Cout == 1) hipLaunchKernelGGL((k_conv3x3_small<4, 1>), g3, dim3(256), 0, tt_stream(stream), p);
+        else if (Cin == 1 && Cout == 2) hipLaunchKernelGGL((k_conv3x3_small<1, 2>), g3, dim3(256), 0, tt_stream(stream), p);
+        else if (Cin == 2 && Cout == 1) hipLaunchKernelGGL((k_conv3x3_small<2, 1>), g3, dim3(256), 0, tt_stream(stream), p);
+        else if (Cin == 4 && Cout == 4) hipLaunchKernelGGL((k_conv3x3_small<4, 4>), g3, dim3(256), 0, tt_stream(stream), p);
+        else return TT_E_UNSUPPORTED;
         TT_LAUNCH_CHECK();
         return 0;
     }
@@ -665,6 +671,33 @@ extern "C" int tt_elu_bwd(const float* dy, const float* y, float* g, int64_t n, 
     if (!dy || !y || !g || n < 0) return TT_E_BADARG;
     if (n == 0) return 0;
     hipLaunchKernelGGL(k_elu_bwd, dim3(grid1d(n / 4 + 1, 256, 4096)), dim3(256), 0, tt_stream(stream), dy, y, g, (long)n);
+    TT_LAUNCH_CHECK();
+    return 0;
+}
+
+// g = act'(a) dy through the saved output y = act(a) (TT_ACT_* of tt_conv2d); n % 4 tail by the first workgroup like k_elu_bwd
+__global__ __launch_bounds__(256) void k_act_bwd_out(const float* __restrict__ dy, const float* __restrict__ y, float* __restrict__ g,
+                                                     long n, int act) {
+    const long n4 = n >> 2;
+    const float4* dy4 = reinterpret_cast<const float4*>(dy);
+    const float4* y4 = reinterpret_cast<const float4*>(y);
+    float4* g4 = reinterpret_cast<float4*>(g);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const float4 a = dy4[i], b = y4[i];
+        g4[i] = make_float4(act_grad_from_out(a.x, b.x, act), act_grad_from_out(a.y, b.y, act),
+                            act_grad_from_out(a.z, b.z, act), act_grad_from_out(a.w, b.w, act));
+    }
+    if (blockIdx.x == 0) {
+        const long i = (n4 << 2) + threadIdx.x;
+        if (i < n) g[i] = act_grad_from_out(dy[i], y[i], act);
+    }
+}
+
+extern "C" int tt_act_bwd(const float* dy, const float* y, float* g, int64_t n, int act, void* stream) {
+    if (!dy || !y || !g || n < 0 || act < TT_ACT_NONE || act > TT_ACT_SIGMOID) return TT_E_BADARG;
+    if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(g)) & 15) return TT_E_BADARG;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_act_bwd_out, dim3(grid1d(n / 4 + 1, 256, 4096)), dim3(256), 0, tt_stream(stream), dy, y, g, (long)n, act);
     TT_LAUNCH_CHECK();
     return 0;
 }

@@ -403,7 +403,8 @@ __device__ __forceinline__ void fft1024_wave(float2 (&v)[16], float2* lds, const
 }
 
 // forward band kernel: grid (ceil(F/4), Q); one wave per bin
-template <bool COMPLEX_OUT>
+// MAG (tt_cqt_forward_mag): one (B,1,F,T) plane of |c| instead of the two planes -- the magnitude variants' encoder input
+template <bool COMPLEX_OUT, bool MAG = false>
 __global__ __launch_bounds__(256) void k_band_fwd(const float2* __restrict__ X, float* __restrict__ out,
                                                   const int4* __restrict__ bin_tab, const float* __restrict__ window,
                                                   const float2* __restrict__ tw1024, int F, int n_blocks) {
@@ -446,6 +447,16 @@ __global__ __launch_bounds__(256) void k_band_fwd(const float2* __restrict__ X, 
             const float4 p0 = src[0], p1 = src[1];
             o[128 * j + 2 * lane] = float4{p0.x * inv, p0.y * inv, p0.z * inv, p0.w * inv};
             o[128 * j + 2 * lane + 1] = float4{p1.x * inv, p1.y * inv, p1.z * inv, p1.w * inv};
+        }
+    } else if (MAG) {
+        // |c| of the scaled coefficients, as torch's norm over the re / im channel of tt_cqt_forward's output computes it
+        float4* om = reinterpret_cast<float4*>(out + (b * F + bin) * Tt + blk * M);
+        auto mag = [inv](float re, float im) { re *= inv; im *= inv; return sqrtf(re * re + im * im); };
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float4* src = reinterpret_cast<const float4*>(lds + 256 * j + 4 * lane);
+            const float4 p0 = src[0], p1 = src[1];           // (re0, im0, re1, im1), (re2, im2, re3, im3)
+            om[64 * j + lane] = float4{mag(p0.x, p0.y), mag(p0.z, p0.w), mag(p1.x, p1.y), mag(p1.z, p1.w)};
         }
     } else {
         float4* ore = reinterpret_cast<float4*>(out + ((b * 2 + 0) * F + bin) * Tt + blk * M);
@@ -566,8 +577,8 @@ static int cqt_set_attrs() {
     return 0;
 }
 
-extern "C" int tt_cqt_forward(const tt_cqt_plan* plan, const float* audio, float* out, void* scratch,
-                              int B, int n_blocks, int out_complex, void* stream) {
+static int cqt_forward(const tt_cqt_plan* plan, const float* audio, float* out, void* scratch, int B, int n_blocks, int out_complex,
+                       bool mag, void* stream) {
     if (!plan || !audio || !out || !scratch || B <= 0 || n_blocks <= 0) return TT_E_BADARG;
     int rc = cqt_set_attrs();
     if (rc) return rc;
@@ -584,7 +595,11 @@ extern "C" int tt_cqt_forward(const tt_cqt_plan* plan, const float* audio, float
                        (unsigned*)nullptr);
     TT_LAUNCH_CHECK();
     dim3 grid((F + 3) / 4, Q);
-    if (out_complex)
+    if (mag)
+        hipLaunchKernelGGL((k_band_fwd<false, true>), grid, dim3(256), 0, st, s.X, out,
+                           reinterpret_cast<const int4*>(plan->bin_tab), plan->window,
+                           reinterpret_cast<const float2*>(plan->tw1024), F, n_blocks);
+    else if (out_complex)
         hipLaunchKernelGGL(k_band_fwd<true>, grid, dim3(256), 0, st, s.X, out,
                            reinterpret_cast<const int4*>(plan->bin_tab), plan->window,
                            reinterpret_cast<const float2*>(plan->tw1024), F, n_blocks);
@@ -594,6 +609,16 @@ extern "C" int tt_cqt_forward(const tt_cqt_plan* plan, const float* audio, float
                            reinterpret_cast<const float2*>(plan->tw1024), F, n_blocks);
     TT_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int tt_cqt_forward(const tt_cqt_plan* plan, const float* audio, float* out, void* scratch,
+                              int B, int n_blocks, int out_complex, void* stream) {
+    return cqt_forward(plan, audio, out, scratch, B, n_blocks, out_complex, false, stream);
+}
+
+extern "C" int tt_cqt_forward_mag(const tt_cqt_plan* plan, const float* audio, float* out, void* scratch, int B, int n_blocks,
+                                  void* stream) {
+    return cqt_forward(plan, audio, out, scratch, B, n_blocks, 0, true, stream);
 }
 
 extern "C" int tt_cqt_inverse(const tt_cqt_plan* plan, const float* coeffs, float* audio, void* scratch,

@@ -28,6 +28,10 @@
 #define tt_convin16_bwd tt_convin16_bwd_h
 #define tt_convout16_fwd tt_convout16_fwd_h
 #define tt_convout16_bwd tt_convout16_bwd_h
+#define tt_convin16_1_fwd tt_convin16_1_fwd_h
+#define tt_convin16_1_bwd tt_convin16_1_bwd_h
+#define tt_convout16_1_fwd tt_convout16_1_fwd_h
+#define tt_convout16_1_bwd tt_convout16_1_bwd_h
 #define ttx_red_defer ttx_red_defer_h
 #define ttx_wprep_done ttx_wprep_done_h
 #define ttx_gate_dx ttx_gate_dx_h

@@ -154,6 +154,20 @@ __global__ __launch_bounds__(256) void k_act_bwd(const float* __restrict__ c, co
     }
 }
 
+// TimbreTrapMag.to_activations (reference modules.py:994): tanh of the 1-channel magnitude logits; backward through the saved output
+// in torch's order, dact (1 - a a)
+__global__ __launch_bounds__(256) void k_act1_fwd(const float* __restrict__ c, float* __restrict__ act, long n) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) act[i] = tanhf(c[i]);
+}
+
+__global__ __launch_bounds__(256) void k_act1_bwd(const float* __restrict__ act, const float* __restrict__ dact, float* __restrict__ dc,
+                                                  long n) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const float a = act[i];
+        dc[i] = dact[i] * (1.f - a * a);
+    }
+}
+
 // A workgroup = 64 consecutive frames x 4 quarters of the F bins (wave = quarter, so every load is 256 contiguous bytes); the
 // quarters meet in LDS in a fixed order.  (One thread per frame looping all 540 bins twice left the launch at 65,536 threads of
 // dependent loads: 0.43 ms for 0.42 GB; round 3.)
@@ -330,6 +344,20 @@ extern "C" int tt_activations_fwd(const float* coeffs, float* act, int B, int F,
     if (!coeffs || !act || B <= 0 || F <= 0 || T <= 0) return TT_E_BADARG;
     const long FT = (long)F * T;
     hipLaunchKernelGGL(k_act_fwd, dim3(nblocks(B * FT, 4) * 4), dim3(256), 0, tt_stream(stream), coeffs, act, B, FT);
+    TT_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int tt_activations1_fwd(const float* coeffs, float* act, int64_t n, void* stream) {
+    if (!coeffs || !act || n <= 0) return TT_E_BADARG;
+    hipLaunchKernelGGL(k_act1_fwd, dim3(nblocks(n, 4) * 4), dim3(256), 0, tt_stream(stream), coeffs, act, (long)n);
+    TT_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int tt_activations1_bwd(const float* act, const float* dact, float* dcoeffs, int64_t n, void* stream) {
+    if (!act || !dact || !dcoeffs || n <= 0) return TT_E_BADARG;
+    hipLaunchKernelGGL(k_act1_bwd, dim3(nblocks(n, 4) * 4), dim3(256), 0, tt_stream(stream), act, dact, dcoeffs, (long)n);
     TT_LAUNCH_CHECK();
     return 0;
 }
@@ -598,7 +626,7 @@ extern "C" int tt_set_cu_limit(int cus) {
     return prev;
 }
 
-extern "C" int tt_version(void) { return 7; }   // 7: tt_channel_sum_ws (the channel sum in a fixed order)   // 6: tt_skip_join16_{fwd,bwd} (the skip joins of the 16-bit path in one pass each way)   // 5: gate links (tt_wide_level_bwd_gated, tt_*_bwd_pregated, tt_latent16_*_{gated,pregated}, tt_gate16)   // 4: any-block-length CQT, tt_set_loss_scale, tt_adamw_step(skipped)   // 3: bf16 channels-last entry points (tt_wide_*, tt_sconv16_*, tt_tconv16_*, tt_latent16_*, tt_conv{in,out}16_*)
+extern "C" int tt_version(void) { return 8; }   // 8: the magnitude variants (tt_cqt_forward_mag, tt_magnitude, tt_decibels, tt_act_bwd, TT_ACT_RELU / TT_ACT_SIGMOID, tt_activations1_*)   // 7: tt_channel_sum_ws (the channel sum in a fixed order)   // 6: tt_skip_join16_{fwd,bwd} (the skip joins of the 16-bit path in one pass each way)   // 5: gate links (tt_wide_level_bwd_gated, tt_*_bwd_pregated, tt_latent16_*_{gated,pregated}, tt_gate16)   // 4: any-block-length CQT, tt_set_loss_scale, tt_adamw_step(skipped)   // 3: bf16 channels-last entry points (tt_wide_*, tt_sconv16_*, tt_tconv16_*, tt_latent16_*, tt_conv{in,out}16_*)
 extern "C" const char* tt_arch(void) { return "gfx950"; }
 extern "C" const char* tt_error_string(int code) {
     if (code == 0) return "ok";

@@ -21,7 +21,7 @@ LIB_PATH = os.path.join(PKG_ROOT, 'lib', 'libttrap_hip.so')
 if os.environ.get('TTRAP_LIB'):                         # tuning: an alternative build of the same sources (tools/build_variant.sh)
     LIB_PATH = os.path.join(PKG_ROOT, 'lib', os.environ['TTRAP_LIB'])
 SOURCES = ['cqt.hip', 'cqt_generic.hip', 'conv_generic.hip', 'conv_mfma.hip', 'conv_small.hip', 'conv_wide_bf16.hip', 'conv_level_bf16.hip', 'conv_stride_bf16.hip',
-           'latent_bf16.hip', 'conv_edge_bf16.hip', 'gemm.hip', 'losses.hip',
+           'latent_bf16.hip', 'conv_edge_bf16.hip', 'gemm.hip', 'losses.hip', 'magnitude.hip',
            # the 16-bit channels-last sources a second time with fp16 elements (two-line wrappers: #define TT_F16 + #include)
            'conv_wide_f16.hip', 'conv_level_f16.hip', 'conv_stride_f16.hip', 'latent_f16.hip', 'conv_edge_f16.hip',
            # fp32-class inference blocks on split fp16 operands
@@ -62,6 +62,13 @@ _PROTOS = {
     'tt_conv2d': (c_int, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, L, L, L, L, I, P]),
     'tt_conv2d_wgrad': (c_int, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, L, L, L, L, P]),
     'tt_elu_bwd': (c_int, [P, P, P, L, P]),
+    'tt_act_bwd': (c_int, [P, P, P, L, I, P]),
+    'tt_cqt_forward_mag': (c_int, [ctypes.POINTER(CqtPlan), P, P, P, I, I, P]),
+    'tt_magnitude': (c_int, [P, P, L, L, P]),
+    'tt_decibels_scratch_bytes': (c_int64, [L]),
+    'tt_decibels': (c_int, [P, P, L, L, I, P, P]),
+    'tt_activations1_fwd': (c_int, [P, P, L, P]),
+    'tt_activations1_bwd': (c_int, [P, P, P, L, P]),
     'tt_resblock_fwd': (c_int, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     'tt_resblock_bwd': (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     'tt_wide_scratch_bytes': (c_int64, [I, I, I, I]),
@@ -114,6 +121,10 @@ _PROTOS = {
     'tt_convin16_bwd': (c_int, [P, P, P, P, P, P, P, P, I, I, I, P]),
     'tt_convout16_fwd': (c_int, [P, P, P, P, I, I, I, P]),
     'tt_convout16_bwd': (c_int, [P, P, P, P, P, P, P, I, I, I, P]),
+    'tt_convin16_1_fwd': (c_int, [P, P, P, P, I, I, I, P]),
+    'tt_convin16_1_bwd': (c_int, [P, P, P, P, P, P, P, P, I, I, I, P]),
+    'tt_convout16_1_fwd': (c_int, [P, P, P, P, I, I, I, I, P]),
+    'tt_convout16_1_bwd': (c_int, [P, P, P, P, P, P, P, P, I, I, I, I, P]),
     'tt_sconv_fwd': (c_int, [P, P, P, P, I, I, I, I, P]),
     'tt_wgrad_scratch_floats': (c_int64, []),
     'tt_sconv_bwd': (c_int, [P, P, P, P, P, P, P, P, I, I, I, I, P]),
@@ -153,7 +164,8 @@ HALF_TWINS = ('tt_wide_level_scratch_bytes', 'tt_wide_level_bwd', 'tt_wide_level
               'tt_wide_rb_bwd_fused', 'tt_wide_onepass_scratch_bytes', 'tt_wide_rb_bwd_onepass', 'tt_wide_rb_bwd_is_onepass',
               'tt_stride16_scratch_bytes', 'tt_sconv16_fwd', 'tt_sconv16_bwd', 'tt_tconv16_fwd', 'tt_tconv16_bwd', 'tt_latent16_scratch_bytes',
               'tt_latent16_contract', 'tt_latent16_expand', 'tt_latent16_wgrad', 'tt_edge16_scratch_bytes', 'tt_convin16_fwd', 'tt_convin16_bwd',
-              'tt_convout16_fwd', 'tt_convout16_bwd', 'tt_scaled_add16', 'tt_dot16', 'tt_skip_join16_fwd', 'tt_skip_join16_bwd')
+              'tt_convout16_fwd', 'tt_convout16_bwd', 'tt_convin16_1_fwd', 'tt_convin16_1_bwd', 'tt_convout16_1_fwd', 'tt_convout16_1_bwd',
+              'tt_scaled_add16', 'tt_dot16', 'tt_skip_join16_fwd', 'tt_skip_join16_bwd')
 for _n in HALF_TWINS:
     _PROTOS[_n + '_h'] = _PROTOS[_n]
 EXPORTED_SYMBOLS = tuple(_PROTOS)

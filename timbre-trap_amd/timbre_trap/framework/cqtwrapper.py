@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from .. import _hip
-from . import nsgt_plan
+from . import nsgt_plan, ops
 
 _TABLES = ('tw675', 'tw49', 'twNc', 'twN', 'tw1024', 'bin_tab', 'window', 'dual', 'gat_off', 'gat_idx')
 _GENERIC_TABLES = ('chirp', 'bfilt', 'twP', 'twM', 'bin_tab', 'window', 'dual', 'gat_off', 'gat_idx', 'pos_bin')
@@ -141,6 +141,30 @@ class CQT(nn.Module):
         with torch.no_grad():
             return self._transform(audio, False)
 
+    def magnitude(self, audio):
+        """
+        ``to_magnitude(forward(audio))`` in one pass: audio (B x 1 x N) -> magnitudes (B x F x T), the input of the magnitude variants
+        (reference modules.py:948, :1019).  The reference configuration writes |c| from the transform's own epilogue
+        (tt_cqt_forward_mag: the two coefficient planes never reach memory); other block lengths compose the any-length transform with
+        tt_magnitude.
+        """
+        if not self._fast:
+            return self.to_magnitude(self.forward(audio))
+        with torch.no_grad():
+            a, lead = self._prepare_audio(audio)
+            B, n_blocks = a.size(0), a.size(1) // self.block_length
+            lib = _hip.lib()
+            ps = self._plan_struct(a.device)
+            scratch = self._scratch(lib, ps, B * n_blocks, a.device)
+            out = torch.empty((B, self.n_bins, n_blocks * self.max_window_length), dtype=torch.float32, device=a.device)
+            with _hip.timed('cqt_forward_mag'):
+                _hip.check(lib.tt_cqt_forward_mag(ctypes.byref(ps), _hip.ptr(a), _hip.ptr(out), _hip.ptr(scratch), B, n_blocks,
+                                                  _hip.stream_ptr()), 'tt_cqt_forward_mag')
+            # the shapes of to_magnitude(forward(audio)): (B,1,N) -> (B,F,T), any other lead -> (*lead, F, T)
+            if len(lead) != 2:
+                out = out.reshape(*lead, *out.shape[1:])
+            return out
+
     def decode(self, coefficients):
         """
         Invert CQT spectral coefficients to synthesize audio (reference cqtwrapper.py:184-213).
@@ -196,16 +220,26 @@ class CQT(nn.Module):
         return torch.view_as_complex(coefficients.contiguous())
 
     @staticmethod
+    def _device_path(t):
+        # fp32 GPU tensors outside autograd take the kernels; CPU tensors and inputs that require grad keep the torch expression
+        return t.is_cuda and t.dtype == torch.float32 and not t.requires_grad
+
+    @staticmethod
     def to_magnitude(coefficients):
-        """L2 norm over the real/imaginary channel (cqtwrapper.py:122-141)."""
+        """L2 norm over the real/imaginary channel (cqtwrapper.py:122-141); GPU: tt_magnitude."""
+        if CQT._device_path(coefficients) and coefficients.dim() >= 3 and coefficients.size(-3) == 2 and coefficients.numel() > 0:
+            return ops.magnitude(coefficients)
         return coefficients.norm(p=2, dim=-3)
 
     @staticmethod
     def to_decibels(magnitude, rescale=True):
         """
         Amplitude -> dB per track with an 80 dB floor, optionally rescaled to [0, 1]
-        (cqtwrapper.py:143-182; torchaudio AmplitudeToDB('amplitude', top_db=80) restated).
+        (cqtwrapper.py:143-182; torchaudio AmplitudeToDB('amplitude', top_db=80) restated).  GPU: tt_decibels, the item maxima and the
+        map in two launches for the whole batch.
         """
+        if CQT._device_path(magnitude) and magnitude.dim() >= 1 and 0 < magnitude.size(0) <= 65535 and magnitude.numel() > 0:
+            return ops.decibels(magnitude, rescale)
         decibels = list()
         for m in magnitude:
             d = 20.0 * torch.log10(torch.clamp(m, min=1e-10))

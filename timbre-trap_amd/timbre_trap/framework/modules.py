@@ -21,7 +21,7 @@ import torch.nn as nn
 from . import CQT
 from . import ops
 from .. import _hip
-from .ops import ACT_ELU, ACT_NONE, ConvCfg
+from .ops import ACT_ELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, ConvCfg
 
 __all__ = [
     'TimbreTrap',
@@ -202,11 +202,12 @@ class Decoder(nn.Module):
         self.block4 = DecoderBlock(channels[3], channels[4], stride=2, padding=padding[3])
         self.convout = nn.Conv2d(channels[4], 2, kernel_size=3, padding='same')
 
-    def forward(self, latents, encoder_embeddings=None, indicator=None, pair=False):
+    def forward(self, latents, encoder_embeddings=None, indicator=None, pair=False, act=ACT_NONE):
         """``indicator``: None (latents carry the switch channel, the reference's call) or its constant value (then latents have
         one channel less and ops.latent_decode supplies it).  ``pair`` (TimbreTrap.decode_pair): the batch is two batches back to
         back; returns their two logits tensors.  ``encoder_embeddings``: the scaled embeddings (reference modules.py:569-589) or
-        ops.SkipJoin descriptors (TimbreTrap.skip_joins: weight and join in one pass; with ``pair`` each serves both halves)."""
+        ops.SkipJoin descriptors (TimbreTrap.skip_joins: weight and join in one pass; with ``pair`` each serves both halves).
+        ``act``: a nonlinearity behind convout, applied in its epilogue (the magnitude variants' decode: TimbreTrap.OUT_ACT)."""
         c = self.convin[0]
         skips = None if encoder_embeddings is None else list(encoder_embeddings)[::-1]
         # (inside ops.x3_chain_scope, no skip connections: the head hands a split-operand tensor to block1's transposed layer)
@@ -228,8 +229,8 @@ class Decoder(nn.Module):
                 y = ops.skip_join(y, skips[i + 1])
         o = self.convout
         if pair:
-            return ops.conv_out_pair(y, o.weight, o.bias)
-        return ops.conv(y, o.weight, o.bias, ConvCfg(3, 3, 1, 1, 1, 1, 'conv', 0, ACT_NONE))
+            return ops.conv_out_pair(y, o.weight, o.bias, act)
+        return ops.conv(y, o.weight, o.bias, ConvCfg(3, 3, 1, 1, 1, 1, 'conv', 0, act))
 
 
 class TimbreTrap(nn.Module):
@@ -240,6 +241,8 @@ class TimbreTrap(nn.Module):
     """
 
     PAIR_DECODE = os.environ.get('TTRAP_PAIR_DECODE', '1') != '0'
+    # the nonlinearity every decoder output goes through (decode, decode_pair): none here, relu / sigmoid in the magnitude variants
+    OUT_ACT = ACT_NONE
 
     def __init__(self, sample_rate, n_octaves, bins_per_octave, secs_per_block=3,
                  latent_size=None, model_complexity=1, skip_connections=False):
@@ -280,9 +283,9 @@ class TimbreTrap(nn.Module):
         if ops.cl16_mode():
             # the 16-bit latent head takes the indicator as a constant channel: no concatenated copy of the latents, and their
             # gradient comes back contiguous
-            return self.decoder(latents, embeddings, indicator=value)
+            return self.decoder(latents, embeddings, indicator=value, act=self.OUT_ACT)
         indicator = torch.full_like(latents[..., :1, :], value)
-        return self.decoder(torch.cat((latents, indicator), dim=-2), embeddings)
+        return self.decoder(torch.cat((latents, indicator), dim=-2), embeddings, act=self.OUT_ACT)
 
     def decode_pair(self, latents, embeddings=None):
         """(decode(latents, embeddings), decode(latents, embeddings, True)) -- the reconstruction and the transcription of the same
@@ -295,7 +298,7 @@ class TimbreTrap(nn.Module):
         if self.PAIR_DECODE and (embeddings is None or joins) and ops.cl16_mode() and torch.is_grad_enabled() and latents.dim() == 3:
             ones = torch.ones_like(latents[..., :1, :])
             z = torch.cat((torch.cat((latents, ones), dim=-2), torch.cat((latents, torch.zeros_like(ones)), dim=-2)), dim=0)
-            return self.decoder(z, embeddings, pair=True)
+            return self.decoder(z, embeddings, pair=True, act=self.OUT_ACT)
         return self.decode(latents, embeddings), self.decode(latents, embeddings, True)
 
     def _inference(self, audio, transcribe=False, check=True):
@@ -334,6 +337,7 @@ class TimbreTrap(nn.Module):
 
     def _chunked(self, audio, transcribe):
         B, F = audio.size(0), self.sliCQ.n_bins
+        K = self.decoder.convout.out_channels              # channels of a chunk's output: 2, or 1 in the magnitude variants
         block, M = self.sliCQ.block_length, self.sliCQ.max_window_length
         audio = self.sliCQ.pad_to_block_length(audio)
         hop = block // 2
@@ -341,7 +345,7 @@ class TimbreTrap(nn.Module):
         n_chunks = (audio.size(-1) - hop) // hop
         window = torch.signal.windows.hann(M, dtype=torch.float32, device=audio.device)
         n_frames = self.sliCQ.get_expected_frames(audio.size(-1))
-        coefficients = torch.zeros((B, 2, F, n_frames), dtype=torch.float32, device=audio.device)
+        coefficients = torch.zeros((B, K, F, n_frames), dtype=torch.float32, device=audio.device)
 
         # (B,1,n_chunks,block) view of the overlapping chunks
         chunks = audio.unfold(-1, block, hop)
@@ -351,17 +355,24 @@ class TimbreTrap(nn.Module):
         for c0 in range(0, n_chunks, per_pass):
             c1 = min(n_chunks, c0 + per_pass)
             batch = chunks[:, :, c0:c1].permute(2, 0, 1, 3).reshape((c1 - c0) * B, 1, block)
-            out = self._inference(batch, transcribe, check=False)     # ((c1 - c0) * B, 2, F, M), chunk-major
+            out = self._inference(batch, transcribe, check=False)     # ((c1 - c0) * B, K, F, M), chunk-major
             out = out.float().contiguous()                            # the kernel reads contiguous fp32 chunks (a no-op for the stock decoder)
+            if out.shape != ((c1 - c0) * B, K, F, M):
+                raise RuntimeError('chunk outputs of shape %s, expected %s' % (tuple(out.shape), ((c1 - c0) * B, K, F, M)))
             # out[b, :, :, i*M/2 : i*M/2 + M] += window * chunk_i, ascending i: the reference's accumulation order (tt_window_ola)
             if M % 8 == 0 and n_frames % 4 == 0:
-                _hip.check(lib.tt_window_ola(_hip.ptr(out), _hip.ptr(window), _hip.ptr(coefficients), B * 2 * F, M, c0, c1, n_frames,
+                _hip.check(lib.tt_window_ola(_hip.ptr(out), _hip.ptr(window), _hip.ptr(coefficients), B * K * F, M, c0, c1, n_frames,
                                              _hip.stream_ptr()), 'tt_window_ola')
             else:       # frame counts the kernel's 16-byte accesses do not cover: the same sums as strided adds, same order
-                out = out.view(c1 - c0, B, 2, F, M)
+                out = out.view(c1 - c0, B, K, F, M)
                 for i in range(c0, c1):
                     coefficients[..., i * (M // 2): i * (M // 2) + M] += window * out[i - c0]
-        return coefficients[..., M // 2: -M // 2]
+        coefficients = coefficients[..., M // 2: -M // 2]
+        if K == 1:
+            # the reference adds the (B,1,F,M) chunk outputs into a zeros((B,2,F,T)) buffer (modules.py:240-263): broadcasting leaves two
+            # equal channels, and transcribe / reconstruct see that (B,2,F,T) tensor
+            coefficients = torch.cat((coefficients, coefficients), dim=1)
+        return coefficients
 
     def to_activations(self, coefficients):
         """logits (B,2,F,T) -> activations (B,F,T) in [0,1): tanh of the complex magnitude."""
@@ -394,9 +405,9 @@ class TimbreTrap(nn.Module):
 
 class _OutOfScopeVariant(TimbreTrap):
     """
-    The ablation variants of the reference (modules.py:780-1075) are outside the accelerated hot
-    path.  The names exist so that ``isinstance`` checks in
-    experiments/train.py:406-411 keep working; constructing one raises.
+    The FiLM ablation variant of the reference (modules.py:780-889) is outside the accelerated hot path (a condition-dependent affine
+    map in front of the latent head).  The names exist so that ``isinstance`` checks in experiments/train.py:406-411
+    keep working; constructing one raises.
     """
 
     def __init__(self, *args, **kwargs):
@@ -408,12 +419,57 @@ class TimbreTrapFiLM(_OutOfScopeVariant):
     pass
 
 
-class TimbreTrapMag(_OutOfScopeVariant):
-    pass
+class TimbreTrapMag(TimbreTrap):
+    """
+    Magnitude-CQT (amplitude) variant (reference modules.py:892-997): the encoder takes |c| as ONE channel, the decoder returns one
+    channel through a relu.  The interior -- levels, strided and transposed layers, latent heads, skip joins -- is TimbreTrap's.
+      * encode:          CQT.magnitude (the transform writes |c| from its epilogue) -> (B,1,F,T)
+      * decode:          relu fused into Decoder.convout's epilogue (tt_conv2d TT_ACT_RELU), on every route incl. decode_pair
+      * to_activations:  tanh of the squeezed logits (tt_activations1_fwd)
+      * chunked_inference / transcribe / reconstruct: the 1-channel chunks are cross-faded as one channel and returned as the
+        reference's two equal channels (TimbreTrap._chunked)
+    """
+
+    OUT_ACT = ACT_RELU
+
+    def __init__(self, sample_rate, n_octaves, bins_per_octave, secs_per_block=3,
+                 latent_size=None, model_complexity=1, skip_connections=False):
+        TimbreTrap.__init__(self, sample_rate, n_octaves, bins_per_octave, secs_per_block,
+                            latent_size, model_complexity, skip_connections)
+        # in the reference's order (the default initialisation draws from the RNG in this order)
+        convin_out_channels = self.encoder.convin[0].out_channels
+        convout_in_channels = self.decoder.convout.in_channels
+        self.encoder.convin = nn.Sequential(nn.Conv2d(1, convin_out_channels, kernel_size=3, padding='same'), nn.ELU(inplace=True))
+        self.decoder.convout = nn.Conv2d(convout_in_channels, 1, kernel_size=3, padding='same')
+
+    def _features(self, audio):
+        """The encoder input without its channel dim: magnitudes (B,F,T)."""
+        return self.sliCQ.magnitude(audio)
+
+    def encode(self, audio):
+        """audio (B,1,N) -> (latents (B,D,T), embeddings, {}) from the (B,1,F,T) magnitude features."""
+        return self.encoder(self._features(audio).unsqueeze(-3))
+
+    def to_activations(self, coefficients):
+        """logits (B,1,F,T) -> activations (B,F,T): tanh (reference modules.py:980-997)."""
+        return ops.Activations1Fn.apply(coefficients.squeeze(-3))
 
 
 class TimbreTrapMagDB(TimbreTrapMag):
-    pass
+    """
+    Magnitude-CQT (decibels) variant (reference modules.py:1000-1075): the encoder takes CQT.to_decibels of the magnitudes (per clip,
+    80 dB range, rescaled to [0, 1]: tt_decibels), the decoder's output goes through a sigmoid (fused like TimbreTrapMag's relu), and the
+    activations are the squeezed logits themselves.
+    """
+
+    OUT_ACT = ACT_SIGMOID
+
+    def _features(self, audio):
+        return self.sliCQ.to_decibels(self.sliCQ.magnitude(audio))
+
+    def to_activations(self, coefficients):
+        """logits (B,1,F,T) -> activations (B,F,T): a view (reference modules.py:1058-1075)."""
+        return coefficients.squeeze(-3)
 
 
 class FiLM(nn.Module):

@@ -18,6 +18,8 @@ from .. import _hip
 from .._hip import check, ptr, stream_ptr
 
 ACT_NONE, ACT_ELU = 0, 1
+# the output nonlinearities of the magnitude variants' decoders (include/ttrap.h TT_ACT_RELU / TT_ACT_SIGMOID; tt_conv2d's epilogue)
+ACT_RELU, ACT_SIGMOID = 2, 3
 
 # The fused ResidualConv2dBlock kernels (csrc/conv_mfma.hip, csrc/conv_small.hip) are the default; TTRAP_FUSED=0 composes
 # the block from the general convolution kernels instead (used to cross-check the two on the GPU).
@@ -193,7 +195,7 @@ class ConvFn(torch.autograd.Function):
         ctx.cfg = cfg
         ctx.has_bias = b is not None
         ctx.params = (w, b)
-        ctx.save_for_backward(x, w, y if cfg.act == ACT_ELU else None)
+        ctx.save_for_backward(x, w, y if cfg.act != ACT_NONE else None)
         return y
 
     @staticmethod
@@ -209,6 +211,10 @@ class ConvFn(torch.autograd.Function):
         if cfg.act == ACT_ELU:
             g = torch.empty_like(dy)
             check(lib.tt_elu_bwd(ptr(dy), ptr(y), ptr(g), dy.numel(), st), 'tt_elu_bwd')
+        elif cfg.act != ACT_NONE:                                # relu / sigmoid through the saved output (16-byte aligned operands)
+            dy = dy if dy.data_ptr() % 16 == 0 else dy.clone()
+            g = torch.empty_like(dy)
+            check(lib.tt_act_bwd(ptr(dy), ptr(y), ptr(g), dy.numel(), cfg.act, st), 'tt_act_bwd')
         else:
             g = dy
         dx = dw = db = rw = rb = None
@@ -260,6 +266,11 @@ def conv(x, w, b, cfg, link=None):
         return ConvIn16Fn.apply(x, w, b, link)                   # Encoder.convin feeding the bf16 channels-last interior
     if same3 and cfg.act == ACT_NONE and w.shape == (2, 4, 3, 3) and is_cl16(x):
         return ConvOut16Fn.apply(x, w, b)                        # Decoder.convout leaving it
+    # the one-channel edges of the magnitude variants (TimbreTrapMag / TimbreTrapMagDB)
+    if same3 and cfg.act == ACT_ELU and w.shape == (4, 1, 3, 3) and not is_cl16(x) and cl16_mode():
+        return ConvIn16x1Fn.apply(x, w, b, link)
+    if same3 and cfg.act in (ACT_NONE, ACT_RELU, ACT_SIGMOID) and w.shape == (1, 4, 3, 3) and is_cl16(x):
+        return ConvOut16x1Fn.apply(x, w, b, cfg.act)
     x = to_planar32(x)
     return ConvFn.apply(x, w, b, cfg)
 
@@ -682,12 +693,111 @@ class ConvOut16PairFn(torch.autograd.Function):
         return dx, r1, r2
 
 
-def conv_out_pair(x, w, b):
-    """Conv2d(4, 2, 3, padding 'same') on a batch of two halves -> (first half, second half) (ConvOut16PairFn; else conv + slices)."""
-    if (x.dim() == 4 and x.size(0) % 2 == 0 and is_cl16(x) and w.shape == (2, 4, 3, 3) and b is not None and x.size(3) % 2 == 0
-            and FUSED_RESBLOCK and x.size(2) * x.size(3) * 4 < 2 ** 31):
+class ConvIn16x1Fn(torch.autograd.Function):
+    """Encoder.convin of the magnitude variants (3x3, 1 -> 4, ELU): fp32 planar (B,1,H,T) -> cl16 (tt_convin16_1_*); the GateLink protocol
+    of ConvIn16Fn (the first level's backward may hand dy back gated: y is then not read)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, link=None):
+        _hip.require_cuda(x, w)
+        x = _f32c(x)
+        B, _, H, T = x.shape
+        y = new_cl16(B, 4, H, T, x.device, cl16_dtype())
+        check(lib16(y).tt_convin16_1_fwd(ptr(x), ptr(w), ptr(b), ptr(y), B, H, T, stream_ptr()), 'tt_convin16_1_fwd')
+        ctx.params = (w, b)
+        ctx.link = link
+        if link is not None:
+            link.producer = True
+        ctx.save_for_backward(x, w, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, y = ctx.saved_tensors
+        B, _, H, T = x.shape
+        lib = lib16(y)
+        g = _as_cl16(dy, y.dtype)
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        (dw, r1), (db, r2) = (_grad_target(t) for t in ctx.params)
+        ws = torch.empty(lib.tt_edge16_scratch_bytes(), dtype=torch.uint8, device=x.device)
+        pre = ctx.link is not None and ctx.link.gated
+        with loss_scaled(y.dtype):
+            check(lib.tt_convin16_1_bwd(ptr(x), None if pre else ptr(y), ptr(g), ptr(w), ptr(dx), ptr(dw), ptr(db), ptr(ws), B, H, T,
+                                        stream_ptr()), 'tt_convin16_1_bwd')
+        return dx, r1, r2, None
+
+
+class ConvOut16x1Fn(torch.autograd.Function):
+    """Decoder.convout of the magnitude variants (3x3, 4 -> 1) with their output nonlinearity in the epilogue: cl16 -> fp32 planar
+    (B,1,H,T) (tt_convout16_1_*); the backward gates dy by act'(y) inside the kernel."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, act):
+        B, _, H, T = x.shape
+        y = torch.empty((B, 1, H, T), dtype=torch.float32, device=x.device)
+        check(lib16(x).tt_convout16_1_fwd(ptr(x), ptr(w), ptr(b), ptr(y), B, H, T, act, stream_ptr()), 'tt_convout16_1_fwd')
+        ctx.params, ctx.act = (w, b), act
+        ctx.save_for_backward(x, w, y if act != ACT_NONE else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, y = ctx.saved_tensors
+        B, _, H, T = x.shape
+        lib = lib16(x)
+        dx = new_cl16(B, 4, H, T, x.device, x.dtype)
+        (dw, r1), (db, r2) = (_grad_target(t) for t in ctx.params)
+        ws = torch.empty(lib.tt_edge16_scratch_bytes(), dtype=torch.uint8, device=x.device)
+        with loss_scaled(x.dtype):
+            check(lib.tt_convout16_1_bwd(ptr(x), ptr(y), ptr(_f32c(dy)), ptr(w), ptr(dx), ptr(dw), ptr(db), ptr(ws), B, H, T, ctx.act,
+                                         stream_ptr()), 'tt_convout16_1_bwd')
+        return dx, r1, r2, None
+
+
+class ConvOut16x1PairFn(torch.autograd.Function):
+    """ConvOut16x1Fn on a batch of two halves (TimbreTrap.decode_pair), returning the halves as two tensors like ConvOut16PairFn."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, act):
+        B, _, H, T = x.shape
+        h = B // 2
+        lib, st = lib16(x), stream_ptr()
+        ys = [torch.empty((h, 1, H, T), dtype=torch.float32, device=x.device) for _ in range(2)]
+        for i, y in enumerate(ys):
+            check(lib.tt_convout16_1_fwd(ptr(x[i * h:(i + 1) * h]), ptr(w), ptr(b), ptr(y), h, H, T, act, st), 'tt_convout16_1_fwd')
+        ctx.params, ctx.act = (w, b), act
+        ctx.save_for_backward(x, w, *(ys if act != ACT_NONE else (None, None)))
+        return ys[0], ys[1]
+
+    @staticmethod
+    def backward(ctx, g0, g1):
+        x, w, y0, y1 = ctx.saved_tensors
+        B, _, H, T = x.shape
+        h = B // 2
+        lib, st = lib16(x), stream_ptr()
+        dx = new_cl16(B, 4, H, T, x.device, x.dtype)
+        (dw, r1), (db, r2) = (_grad_target(t) for t in ctx.params)
+        ws = torch.empty(lib.tt_edge16_scratch_bytes(), dtype=torch.uint8, device=x.device)
+        with loss_scaled(x.dtype):
+            for i, (g, y) in enumerate(((g0, y0), (g1, y1))):
+                if g is None:
+                    dx[i * h:(i + 1) * h].zero_()
+                    continue
+                check(lib.tt_convout16_1_bwd(ptr(x[i * h:(i + 1) * h]), ptr(y), ptr(_f32c(g)), ptr(w), ptr(dx[i * h:(i + 1) * h]), ptr(dw),
+                                             ptr(db), ptr(ws), h, H, T, ctx.act, st), 'tt_convout16_1_bwd')
+        return dx, r1, r2, None
+
+
+def conv_out_pair(x, w, b, act=ACT_NONE):
+    """Conv2d(4, 2, 3, padding 'same') on a batch of two halves -> (first half, second half) (ConvOut16PairFn; else conv + slices).
+    ``act``: the output nonlinearity of the magnitude variants (ACT_RELU / ACT_SIGMOID), fused into tt_conv2d's epilogue."""
+    pairable = (x.dim() == 4 and x.size(0) % 2 == 0 and is_cl16(x) and b is not None and x.size(3) % 2 == 0 and FUSED_RESBLOCK
+                and x.size(2) * x.size(3) * 4 < 2 ** 31)
+    if pairable and act == ACT_NONE and w.shape == (2, 4, 3, 3):
         return ConvOut16PairFn.apply(x, w, b)
-    y = conv(x, w, b, ConvCfg(3, 3, 1, 1, 1, 1, 'conv', 0, ACT_NONE))
+    if pairable and w.shape == (1, 4, 3, 3):
+        return ConvOut16x1PairFn.apply(x, w, b, act)             # the magnitude variants' convout, nonlinearity in the epilogue
+    y = conv(x, w, b, ConvCfg(3, 3, 1, 1, 1, 1, 'conv', 0, act))
     h = y.size(0) // 2
     return y[:h], y[h:]
 
@@ -1951,6 +2061,46 @@ class ActivationsFn(torch.autograd.Function):
         return dc
 
 
+class Activations1Fn(torch.autograd.Function):
+    """tanh of the 1-channel magnitude logits, any shape (TimbreTrapMag.to_activations, modules.py:994)."""
+
+    @staticmethod
+    def forward(ctx, coefficients):
+        _hip.require_cuda(coefficients)
+        c = _f32c(coefficients)
+        act = torch.empty_like(c)
+        check(_hip.lib().tt_activations1_fwd(ptr(c), ptr(act), c.numel(), stream_ptr()), 'tt_activations1_fwd')
+        ctx.save_for_backward(act)
+        return act
+
+    @staticmethod
+    def backward(ctx, dact):
+        act, = ctx.saved_tensors
+        dc = torch.empty_like(act)
+        check(_hip.lib().tt_activations1_bwd(ptr(act), ptr(_f32c(dact)), ptr(dc), act.numel(), stream_ptr()), 'tt_activations1_bwd')
+        return dc
+
+
+def magnitude(coefficients):
+    """(..., 2, F, T) fp32 re / im planes -> (..., F, T) magnitudes (tt_magnitude); no autograd."""
+    c = _f32c(coefficients)
+    F, T = c.shape[-2:]
+    out = torch.empty(c.shape[:-3] + (F, T), dtype=torch.float32, device=c.device)
+    check(_hip.lib().tt_magnitude(ptr(c), ptr(out), c.numel() // (2 * F * T), F * T, stream_ptr()), 'tt_magnitude')
+    return out
+
+
+def decibels(m, rescale=True):
+    """Per item of dim 0: 20 log10(max(m, 1e-10)) floored 80 dB below the item's maximum, optionally 1 + (d - max) / 80 (tt_decibels);
+    no autograd."""
+    m = _f32c(m)
+    lib = _hip.lib()
+    ws = torch.empty(lib.tt_decibels_scratch_bytes(m.size(0)), dtype=torch.uint8, device=m.device)
+    out = torch.empty_like(m)
+    check(lib.tt_decibels(ptr(m), ptr(out), m.size(0), m.numel() // m.size(0), int(bool(rescale)), ptr(ws), stream_ptr()), 'tt_decibels')
+    return out
+
+
 class TranscriptionLossFn(torch.autograd.Function):
     """compute_transcription_loss (objectives.py:36-74); gradient w.r.t. the estimate only."""
 
@@ -2041,6 +2191,9 @@ _instrument(WideLevelFn, 'widelevel', lambda x, *a: 'C%d' % x.size(1))
 _instrument(ConvIn16Fn, 'edge16', lambda x, *a: 'in')
 _instrument(ConvOut16Fn, 'edge16', lambda x, *a: 'out')
 _instrument(ConvOut16PairFn, 'edge16', lambda x, *a: 'out')
+_instrument(ConvIn16x1Fn, 'edge16', lambda x, *a: 'in1')
+_instrument(ConvOut16x1Fn, 'edge16', lambda x, *a: 'out1')
+_instrument(ConvOut16x1PairFn, 'edge16', lambda x, *a: 'out1')
 _instrument(Level16Fn, 'widelevel', lambda x, *a: 'C%d' % x.size(1))
 _instrument(Level16JoinFn, 'widelevel', lambda x, *a: 'C%d' % x.size(1))
 _instrument(SConv16Fn, 'sconv16', lambda x, *a: 'C%d' % x.size(1))
@@ -2057,4 +2210,5 @@ _instrument(LatentDecodeFn, 'latdec', lambda z, w, *a: 'C%d' % w.size(1))
 _instrument(SqDiffLossFn, 'sqdiff', lambda a, *r: 'n')
 _instrument(SqDiff2Fn, 'sqdiff2', lambda a, *r: 'n')
 _instrument(ActivationsFn, 'act', lambda c: 'n')
+_instrument(Activations1Fn, 'act1', lambda c: 'n')
 _instrument(TranscriptionLossFn, 'trn', lambda e, *r: 'n')
