@@ -496,9 +496,9 @@ def _autocast_step_vs_oracle(n_clips, n_blocks, n_mpe, record=None, bench_target
     flushed = []
     if monkeypatch is not None:
         orig_flush = ops.flush_pending
-        monkeypatch.setattr(ops, 'flush_pending', lambda link, dx: (flushed.append(len(getattr(link, 'pending', None) or ())), orig_flush(link, dx))[1])
+        monkeypatch.setattr(ops.skip, 'flush_pending', lambda link, dx: (flushed.append(len(getattr(link, 'pending', None) or ())), orig_flush(link, dx))[1])
         rides, orig_ride = [], ops._riding_join
-        monkeypatch.setattr(ops, '_riding_join', lambda ctx_, x0: (lambda r: (rides.append(r is not None), r)[1])(orig_ride(ctx_, x0)))
+        monkeypatch.setattr(ops.skip, '_riding_join', lambda ctx_, x0: (lambda r: (rides.append(r is not None), r)[1])(orig_ride(ctx_, x0)))
     c, g = run['coeffs'].cuda(), run['gt'].cuda()
     pair_calls = _count_calls(monkeypatch, ops.ConvOut16PairFn) if monkeypatch is not None else None
     join_calls = _count_calls(monkeypatch, ops.SkipJoin16Fn) if monkeypatch is not None else None

@@ -237,7 +237,7 @@ def test_fp16_hidden_overflow_surfaces(C, w2sign):
 
 
 def _layer_cases():
-    """(name, build) for every 16-bit layer Function of ops.py: build() -> (fn, 16-bit or fp32 inputs, fp32 parameters, output gradient)."""
+    """(name, build) for every 16-bit layer Function of the ops package: build() -> (fn, 16-bit or fp32 inputs, fp32 parameters, output gradient)."""
     from timbre_trap.framework import modules, ops
     h = torch.float16
 
