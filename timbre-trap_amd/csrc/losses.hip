@@ -34,6 +34,12 @@ __global__ __launch_bounds__(256) void k_finalize(const double* __restrict__ par
     }
 }
 
+// The four squares of one float4, as a double.  The fmas are spelled out: left to the compiler, k_sqdiff_fused contracted
+// d0 * d0 + d1 * d1 into one and k_sqdiff_partial did not, and their "bit-identical" losses came out an fp32 ulp apart.
+__device__ __forceinline__ double sq4(float d0, float d1, float d2, float d3) {
+    return (double)__fmaf_rn(d0, d0, d1 * d1) + (double)__fmaf_rn(d2, d2, d3 * d3);
+}
+
 __global__ __launch_bounds__(256) void k_sqdiff_partial(const float* __restrict__ a, const float* __restrict__ b,
                                                         double* __restrict__ partials, long n) {
     const long n4 = n >> 2;
@@ -43,7 +49,7 @@ __global__ __launch_bounds__(256) void k_sqdiff_partial(const float* __restrict_
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         const float4 x = a4[i], y = b4[i];
         const float d0 = x.x - y.x, d1 = x.y - y.y, d2 = x.z - y.z, d3 = x.w - y.w;
-        acc += (double)(d0 * d0 + d1 * d1) + (double)(d2 * d2 + d3 * d3);
+        acc += sq4(d0, d1, d2, d3);
     }
     if (blockIdx.x == 0) {
         const long i = (n4 << 2) + threadIdx.x;
@@ -69,13 +75,13 @@ __global__ __launch_bounds__(256) void k_sqdiff_fused(const float* __restrict__ 
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         const float4 y = pb[i], x = p1[i];
         const float d0 = x.x - y.x, d1 = x.y - y.y, d2 = x.z - y.z, d3 = x.w - y.w;
-        acc1 += (double)(d0 * d0 + d1 * d1) + (double)(d2 * d2 + d3 * d3);
+        acc1 += sq4(d0, d1, d2, d3);
         const float4 u = float4{s2 * d0, s2 * d1, s2 * d2, s2 * d3};
         float4 v = float4{0.f, 0.f, 0.f, 0.f};
         if (TWO) {
             const float4 z = p2[i];
             const float e0 = z.x - y.x, e1 = z.y - y.y, e2 = z.z - y.z, e3 = z.w - y.w;
-            acc2 += (double)(e0 * e0 + e1 * e1) + (double)(e2 * e2 + e3 * e3);
+            acc2 += sq4(e0, e1, e2, e3);
             v = float4{s2 * e0, s2 * e1, s2 * e2, s2 * e3};
             if (da2) reinterpret_cast<float4*>(da2)[i] = v;
         }
