@@ -551,7 +551,8 @@ int tt_target_activations(const int* bins, const int* frames, int n, const doubl
  * value v (activations in HBM, weights in LDS) is the pair hi = fp16(v), lo = fp16((v - hi) 2^11) and a product is
  * Whi xhi + 2^-11 (Whi xlo + Wlo xhi) on v_mfma_f32_16x16x32_f16 with fp32 accumulators; bias, ELU, residual add in fp32.  Results agree
  * with the fp32 kernels (tt_resblock_fwd) to a few 1e-7 relative; values beyond fp16's range (|v| > 65504) come out non-finite.
- * Forward only (no hidden activation is saved): the no-grad path of ops.residual_level in fp32 mode.
+ * tt_x3_rb_fwd / tt_x3_level_fwd save no hidden activation: the no-grad path of ops.residual_level in fp32 mode.  The chain, strided and latent
+ * entries below are forward only; the block has a training forward and a backward further down (tt_x3_rb_fwd_train / tt_x3_rb_bwd).
  *   tt_x3_bytes      bytes of one activation tensor in the x3 layout [B][H][T][2][C] halves (= B C H T 4)
  *   tt_x3_pack       x (B,C,H,T) fp32 planar -> x3              tt_x3_unpack   the inverse (exact to 2^-23 relative)
  *   tt_x3_rb_fwd     y = ELU(W2 . ELU(W1 (*)_dil x + b1) + b2) + x; x is an x3 tensor, y an x3 tensor (planar_out = 0; x != y) or an
@@ -579,6 +580,39 @@ int tt_x3_rb_fwd(const void* x, const float* w1, const float* b1, const float* w
 int tt_x3_level_fwd(int nblocks, const void* x, int x3_in, void* y, int x3_out, const float* const* w1, const float* const* b1,
                     const float* const* w2, const float* const* b2, const int* dilations, void* ws, int B, int C, int H, int T,
                     void* stream);
+
+/* ---- split-operand TRAINING of the wide residual blocks (csrc/conv_x3.hip; opt-in: ops.X3_TRAIN / TTRAP_X3_TRAIN=1) -----------------
+ * The forward-with-saved-activations and the backward of one ResidualConv2dBlock (reference modules.py:721-777: forward 755-777, and the
+ * autograd backward of those lines that tt_resblock_fwd / tt_resblock_bwd provide on the fp32 matrix instructions) at C = 16, 32,
+ * dilation 1..3, on (hi, lo) fp16 pairs: every matrix product -- the two weight gradients, whose K dimension is pixels, included -- is the
+ * three-term form on v_mfma_f32_16x16x32_f16 with fp32 accumulators; bias sums, ELU' and the residual add are fp32.  All activation-sized
+ * tensors (x, h1, y, dy, dx) are x3 tensors of tt_x3_bytes bytes.
+ *   tt_x3_rb_fwd_train  tt_x3_rb_fwd that also stores h1 = ELU(W1 (*)_dil x + b1) as an x3 tensor (x, y, h1 distinct)
+ *   tt_x3_grad_scale    scale[0] = S, scale[1] = 1 / S (device memory, no host sync): the power of two that puts abs-max(dy[0..n)) into
+ *                       [2^8, 2^9); S = 1 for an all-zero or a non-finite dy.  A pair of halves is exact to 2^-22 relative only above
+ *                       ~2^-15, and activation gradients of a mean-reduced loss sit at 1e-7 .. 1e-10: every x3 GRADIENT tensor carries S.
+ *                       ws: tt_x3_grad_scale_scratch_bytes() bytes
+ *   tt_x3_pack_scaled   x3 = split(x * scale[0])            tt_x3_unpack_scaled   y = join(x3) * scale[1]   (scale = NULL: tt_x3_pack / _unpack)
+ *   tt_x3_rb_bwd        reads what tt_resblock_bwd reads -- the block input x, h1 and the incoming gradient dy (x3, carrying S):
+ *                         g2 = dy ELU'(W2 h1 + b2)      dw2 += sum g2 (x) h1 / S      db2 += sum g2 / S
+ *                         g1 = (W2^T g2) ELU'(h1)       db1 += sum g1 / S             dw1[co][ci][tap] += sum g1[co][p] x[ci][p + tap] / S
+ *                         dx = dy + W1^T (*)_dil g1     an x3 tensor still carrying S (planar_dx = 0) or fp32 planar (B,C,H,T) times 1 / S
+ *                       The weight and bias gradients are summed in a fixed order (per-workgroup partials in ws, then a reduce launch; no
+ *                       float atomics): bit-reproducible.  Powers of two are exact, so S never shows in a result.  dx differs from x, h1, dy;
+ *                       dx = NULL (the block's input wants no gradient) skips the data-gradient launch;
+ *                       ws: tt_x3_rb_bwd_scratch_bytes bytes (g1 as an x3 tensor + the partials).
+ * Range: activations or weights beyond +-65504 come out non-finite, never finite and wrong; a non-finite dy gives non-finite gradients.
+ * There is no fp32 fallback in training (it would take a host sync per level): the caller's finite check on the loss catches it. */
+int tt_x3_rb_fwd_train(const void* x, const float* w1, const float* b1, const float* w2, const float* b2, void* y, int planar_out, void* h1,
+                       int B, int C, int H, int T, int dilation, void* stream);
+int64_t tt_x3_grad_scale_scratch_bytes(void);
+int tt_x3_grad_scale(const float* dy, int64_t n, float* scale, void* ws, void* stream);
+int tt_x3_pack_scaled(const float* x, void* out, const float* scale, int B, int C, int H, int T, void* stream);
+int tt_x3_unpack_scaled(const void* in, float* y, const float* scale, int B, int C, int H, int T, void* stream);
+int64_t tt_x3_rb_bwd_scratch_bytes(int B, int C, int H, int T);
+int tt_x3_rb_bwd(const void* x, const void* h1, const void* dy, const float* w1, const float* w2, const float* b2, void* dx, int planar_dx,
+                 float* dw1, float* db1, float* dw2, float* db2, const float* scale, void* ws, int B, int C, int H, int T, int dilation,
+                 void* stream);
 /* The strided layers between and above the wide levels with split operands, so that level -> strided layer -> level never leaves the
  * x3 layout.  x is an x3 tensor (planar_in = 0) or -- the layer that ENTERS the split-operand part of the network -- an fp32 planar
  * (B,C,H,T) tensor (planar_in = 1); y an x3 tensor (planar_out = 0) or fp32 planar (planar_out = 1):

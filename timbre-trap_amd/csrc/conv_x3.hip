@@ -19,7 +19,13 @@
 //
 // Kernels: k_x3_pack / k_x3_unpack (fp32 planar <-> x3 at the two ends of a level), k_x3_conv<C, D> (one residual block:
 // y = ELU(W2 . ELU(W1 (*)_D x + b1) + b2) + x; persistent, XCD-ordered tile walk; weights of both planes in LDS in operand order,
-// written by every workgroup for itself).  Forward only: training saves fp32 activations for the fp32 backward.
+// written by every workgroup for itself).
+//
+// Training (ops.X3_TRAIN; the second half of this file): k_x3_conv<.., MODE 1> is the same block that also stores the hidden activation
+// h1 = ELU(W1 (*) x + b1) as an x3 tensor (the halves it feeds to the 1x1 product), and the backward runs on split operands too --
+// k_x3_bwd_a (pointwise chain + dW2, db1, db2), k_x3_conv<.., MODE 2> (dx = dy + W1^T (*) g1: the forward's 3x3 product with transposed,
+// mirrored weights), k_x3_wgrad (dW1, K = pixels) and k_x3_reduce (fixed-order sum of the workgroups' dumps).  Every x3 GRADIENT tensor
+// carries a power-of-two factor S chosen on the device from abs-max(dy) (k_x3_absmax / k_x3_scale_fin), see "gradient range" below.
 #define TT_F16 1
 #include "wide_common.h"
 
@@ -135,7 +141,8 @@ template <int C> __device__ __forceinline__ int xswz(int col) { return (col / XL
 
 // ---- layout change at the ends of a level: one thread per eight channels of one pixel ----------------------------------------
 template <int C>
-__global__ __launch_bounds__(NT) void k_x3_pack(const float* __restrict__ x, e16* __restrict__ out, int H, int T, long npix) {
+__global__ __launch_bounds__(NT) void k_x3_pack(const float* __restrict__ x, e16* __restrict__ out, int H, int T, long npix,
+                                                const float* __restrict__ scale) {     // scale: nullptr, or {S, 1 / S}: out = split(x S)
     constexpr int CG = C / 8;
     const long i = (long)blockIdx.x * NT + threadIdx.x;
     const long pix = i / CG;
@@ -144,14 +151,16 @@ __global__ __launch_bounds__(NT) void k_x3_pack(const float* __restrict__ x, e16
     const long plane = (long)H * T;
     const long b = pix / plane, o = pix - b * plane;
     const float* s = x + (b * C + cg * 8) * plane + o;
+    const float sc = scale ? scale[0] : 1.f;
     e16x8 qh, ql;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { e16 h, l; split(s[j * plane], h, l); qh[j] = h; ql[j] = l; }
+    for (int j = 0; j < 8; ++j) { e16 h, l; split(s[j * plane] * sc, h, l); qh[j] = h; ql[j] = l; }
     *reinterpret_cast<e16x8*>(out + pix * 2 * C + cg * 8) = qh;
     *reinterpret_cast<e16x8*>(out + pix * 2 * C + C + cg * 8) = ql;
 }
 template <int C>
-__global__ __launch_bounds__(NT) void k_x3_unpack(const e16* __restrict__ in, float* __restrict__ y, int H, int T, long npix) {
+__global__ __launch_bounds__(NT) void k_x3_unpack(const e16* __restrict__ in, float* __restrict__ y, int H, int T, long npix,
+                                                  const float* __restrict__ scale) {   // y = join(in) / S
     constexpr int CG = C / 8;
     const long i = (long)blockIdx.x * NT + threadIdx.x;
     const long pix = i / CG;
@@ -162,8 +171,9 @@ __global__ __launch_bounds__(NT) void k_x3_unpack(const e16* __restrict__ in, fl
     const e16x8 qh = *reinterpret_cast<const e16x8*>(in + pix * 2 * C + cg * 8);
     const e16x8 ql = *reinterpret_cast<const e16x8*>(in + pix * 2 * C + C + cg * 8);
     float* d = y + (b * C + cg * 8) * plane + o;
+    const float sc = scale ? scale[1] : 1.f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) d[j * plane] = join(qh[j], ql[j]);
+    for (int j = 0; j < 8; ++j) d[j * plane] = join(qh[j], ql[j]) * sc;
 }
 
 // ---- one residual block ---------------------------------------------------------------------------------------------------------
@@ -194,15 +204,24 @@ template <int C, int D> struct XT {
     static constexpr int W1_BYTES = NK * NCT * NPL * 64 * 16;    // [k][ct][plane][lane] x 16 bytes
     static constexpr int W2_BYTES = WREG ? 0 : 2 * 64 * 8;       // C = 16: [plane][lane] x 8 bytes
     static constexpr int LDS_BYTES = TILE_BYTES + W1_BYTES + W2_BYTES;
+    static constexpr int BIAS_BYTES = WREG ? 0 : 128;            // behind LDS_BYTES, MODE 1 at C = 16 only: b1 and b2 (registers: 128 is the cap there)
+    static constexpr int lds_bytes(int mode) { return LDS_BYTES + (mode == 1 ? BIAS_BYTES : 0); }
     static_assert(R * NRG == TH, "rows per wave");
 };
 
 // PLANAR: the output goes out as fp32 (B,C,H,T) instead of x3 -- the last block of a level (saves the unpack pass).
-template <int C, int D, bool PLANAR>
+// MODE 0: the block.  MODE 1 (training forward): the block, and the halves of h1 that feed the 1x1 product also go to `h1out` (x3).
+// MODE 2 (data gradient of the training backward): x = g1 (scaled by S), the 3x3 product takes W1 transposed and mirrored
+// (out channel = ci, contraction = co, tap 8 - k), there is no bias, no ELU and no 1x1 product, and the epilogue adds dy (x3, `dyin`):
+// dx = dy + W1^T (*)_D g1 -- as an x3 tensor still carrying S, or (PLANAR) fp32 multiplied by 1 / S = scale[1].
+template <int C, int D, bool PLANAR, int MODE = 0>
 __global__ __launch_bounds__((XT<C, D>::NTH), (XT<C, D>::MINW)) void k_x3_conv(const e16* __restrict__ x, const float* __restrict__ w1,
                                                                                const float* __restrict__ b1, const float* __restrict__ w2,
                                                                                const float* __restrict__ b2, void* __restrict__ yout,
-                                                                               int B, int H, int T, int tiles_h, int tiles_t, int ntiles) {
+                                                                               int B, int H, int T, int tiles_h, int tiles_t, int ntiles,
+                                                                               e16* __restrict__ h1out, const e16* __restrict__ dyin,
+                                                                               const float* __restrict__ scale) {
+    constexpr bool DX = MODE == 2;
     using G = XT<C, D>;
     using L = XL<C>;
     constexpr int NTH = G::NTH, NCT = G::NCT, NK = G::NK, R = G::R, PB = L::PB, CG = L::CG, NPL = G::NPL;
@@ -225,7 +244,7 @@ __global__ __launch_bounds__((XT<C, D>::NTH), (XT<C, D>::MINW)) void k_x3_conv(c
             if (C == 32) { tap = k; kc = 8 * lg + j; }
             else { tap = 2 * k + (lg >> 1); kc = 8 * (lg & 1) + j; }
             const int mo = chan_of<C>(ct, ln);                   // output channel of row n
-            const float wv = tap < 9 ? w1[(mo * C + kc) * 9 + tap] : 0.f;
+            const float wv = tap < 9 ? (DX ? w1[(kc * C + mo) * 9 + (8 - tap)] : w1[(mo * C + kc) * 9 + tap]) : 0.f;
             e16 h, lo_; split(wv, h, lo_); qh[j] = h; ql[j] = lo_;
         }
         if constexpr (!WREG) *reinterpret_cast<e16x8*>(w1img + ((long)((k * NCT + ct) * NPL + 0) * 64 + l) * 16) = qh;
@@ -238,14 +257,17 @@ __global__ __launch_bounds__((XT<C, D>::NTH), (XT<C, D>::MINW)) void k_x3_conv(c
 #pragma unroll
             for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) WH[k][ct][j] = (e16)w1[(chan_of<C>(ct, n) * C + 8 * g + j) * 9 + k];
+                for (int j = 0; j < 8; ++j)
+                    WH[k][ct][j] = (e16)(DX ? w1[((8 * g + j) * C + chan_of<C>(ct, n)) * 9 + (8 - k)] : w1[(chan_of<C>(ct, n) * C + 8 * g + j) * 9 + k]);
+        if constexpr (!DX) {
 #pragma unroll
-        for (int ct = 0; ct < NCT; ++ct)
+            for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                e16 h, lo_; split(w2[chan_of<C>(ct, n) * C + 8 * g + j], h, lo_); A2H[ct][j] = h; A2L[ct][j] = lo_;
-            }
-    } else {
+                for (int j = 0; j < 8; ++j) {
+                    e16 h, lo_; split(w2[chan_of<C>(ct, n) * C + 8 * g + j], h, lo_); A2H[ct][j] = h; A2L[ct][j] = lo_;
+                }
+        }
+    } else if constexpr (!DX) {
         for (int e = tid; e < 64; e += NTH) {
             e16x4 qh, ql;
 #pragma unroll
@@ -254,9 +276,20 @@ __global__ __launch_bounds__((XT<C, D>::NTH), (XT<C, D>::MINW)) void k_x3_conv(c
             *reinterpret_cast<e16x4*>(w2img + (long)(64 + e) * 8) = ql;
         }
     }
+    // BLDS: the biases are re-read from LDS where they are used.  This and the opaque statements in the epilogue below steer the register
+    // allocator under the 128-register cap of four waves per SIMD: tuned against AMD clang 22.0.0git (ROCm 7.2.0), where every k_x3_conv
+    // MODE 1 instance at C = 16 takes 112-128 VGPRs and no scratch.  After a toolchain change re-check with
+    // -Rpass-analysis=kernel-resource-usage (tools/resource_usage.py): a spill here costs speed, never correctness.
+    constexpr bool BLDS = MODE == 1 && C == 16;
+    float* bimg = reinterpret_cast<float*>(w2img + G::W2_BYTES);
     float b1r[NCH], b2r[NCH];
+    if constexpr (BLDS) {
+        if (tid < 16) { bimg[tid] = b1[tid]; bimg[16 + tid] = b2[tid]; }
+    } else {
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) { b1r[j] = b1[NCH * g + j]; b2r[j] = b2[NCH * g + j]; }
+        for (int j = 0; j < NCH; ++j) { b1r[j] = DX ? 0.f : b1[NCH * g + j]; b2r[j] = DX ? 0.f : b2[NCH * g + j]; }
+    }
+    const float unscale = (DX && PLANAR) ? scale[1] : 1.f;
 
     const int c0 = (wave % G::NCG) * 16, r0 = (wave / G::NCG) * R;
     const e16* zero = reinterpret_cast<const e16*>(&g_wzero16);
@@ -290,6 +323,11 @@ __global__ __launch_bounds__((XT<C, D>::NTH), (XT<C, D>::MINW)) void k_x3_conv(c
 #endif
         if (h0 + r0 >= H) continue;
         f32x4 am[R][NCT], al[R][NCT];                            // hi x hi (bias as initial value) and the two cross terms
+        if constexpr (BLDS) {
+            const f32x4 q = *reinterpret_cast<const f32x4*>(bimg + 4 * g);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) b1r[j] = q[j];
+        }
 #pragma unroll
         for (int rr = 0; rr < R; ++rr)
 #pragma unroll
@@ -335,10 +373,26 @@ __global__ __launch_bounds__((XT<C, D>::NTH), (XT<C, D>::MINW)) void k_x3_conv(c
             const int h = h0 + r0 + rr;
             if (h >= H) break;
             const long pix = ((long)b * H + h) * T + t;
-            const int colc = c0 + n + D, swc = xswz<C>(colc);
+            // BLDS (128 registers is the cap): the lane's indices pass through an opaque statement, so that the row's LDS and store addresses
+            // are formed here, not once per kernel and then held (and spilled) across the whole tile loop
+            int ne = n, ge = g;
+            if constexpr (BLDS) asm volatile("" : "+v"(ne), "+v"(ge));
+            const int colc = c0 + ne + D, swc = xswz<C>(colc);
             const unsigned char* pxc = smem + ((long)(r0 + rr + D) * G::RW + colc) * PB;
             float out[NCH];
-            if constexpr (C == 32) {
+            if constexpr (DX) {
+#pragma unroll
+                for (int j = 0; j < NCH; ++j) out[j] = __builtin_fmaf(al[rr][j >> 2][j & 3], LO_INV, am[rr][j >> 2][j & 3]);
+                if (valid) {                                     // the incoming gradient of the block's output: this lane's channels of its pixel
+                    typedef typename std::conditional<C == 32, e16x8, e16x4>::type vec_t;
+                    const vec_t dh = *reinterpret_cast<const vec_t*>(dyin + pix * 2 * C + NCH * g);
+                    const vec_t dl = *reinterpret_cast<const vec_t*>(dyin + pix * 2 * C + C + NCH * g);
+                    float res[NCH];
+                    join_v(dh, dl, res);
+#pragma unroll
+                    for (int j = 0; j < NCH; ++j) out[j] = (out[j] + res[j]) * unscale;
+                }
+            } else if constexpr (C == 32) {
                 e16x8 hh, hl;
                 float hv[8];
 #pragma unroll
@@ -347,6 +401,11 @@ __global__ __launch_bounds__((XT<C, D>::NTH), (XT<C, D>::MINW)) void k_x3_conv(c
                     hv[4 + j] = elu1(__builtin_fmaf(al[rr][1][j], LO_INV, am[rr][1][j]));
                 }
                 split_v<true>(hv, hh, hl);
+                if constexpr (MODE == 1)
+                    if (valid) {
+                        *reinterpret_cast<e16x8*>(h1out + pix * 2 * C + 8 * g) = hh;
+                        *reinterpret_cast<e16x8*>(h1out + pix * 2 * C + C + 8 * g) = hl;
+                    }
                 f32x4 zm[2], zl[2];
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct) {
@@ -367,13 +426,25 @@ __global__ __launch_bounds__((XT<C, D>::NTH), (XT<C, D>::MINW)) void k_x3_conv(c
 #pragma unroll
                 for (int j = 0; j < 4; ++j) hv[j] = elu1(__builtin_fmaf(al[rr][0][j], LO_INV, am[rr][0][j]));
                 split_v<true>(hv, hh, hl);
+                if constexpr (MODE == 1)
+                    if (valid) {                                 // uniform row base + a 32-bit lane offset: one address register (128 is the cap)
+                        e16* hp = h1out + (((long)b * H + h) * T + t0) * 2 * C + (unsigned)((c0 + ne) * 2 * C + 4 * ge);
+                        *reinterpret_cast<e16x4*>(hp) = hh;
+                        *reinterpret_cast<e16x4*>(hp + C) = hl;
+                        asm volatile("" ::: "memory");           // keeps the residual's LDS reads below the stores (registers)
+                    }
+                if constexpr (BLDS) {
+                    const f32x4 q = *reinterpret_cast<const f32x4*>(bimg + 16 + 4 * g);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) b2r[j] = q[j];
+                }
                 const s16x4 a2h = *reinterpret_cast<const s16x4*>(w2img + (long)lane * 8);
                 const s16x4 a2l = *reinterpret_cast<const s16x4*>(w2img + (long)(64 + lane) * 8);
                 const f32x4 zm = mma16(a2h, __builtin_bit_cast(s16x4, hh), f32x4{b2r[0], b2r[1], b2r[2], b2r[3]});
                 f32x4 zl = mma16(a2h, __builtin_bit_cast(s16x4, hl), f32x4{0.f, 0.f, 0.f, 0.f});
                 zl = mma16(a2l, __builtin_bit_cast(s16x4, hh), zl);
-                const e16x4 ch = *reinterpret_cast<const e16x4*>(pxc + 16 * ((g >> 1) ^ swc) + 8 * (g & 1));
-                const e16x4 cl = *reinterpret_cast<const e16x4*>(pxc + 16 * ((CG + (g >> 1)) ^ swc) + 8 * (g & 1));
+                const e16x4 ch = *reinterpret_cast<const e16x4*>(pxc + 16 * ((ge >> 1) ^ swc) + 8 * (ge & 1));
+                const e16x4 cl = *reinterpret_cast<const e16x4*>(pxc + 16 * ((CG + (ge >> 1)) ^ swc) + 8 * (ge & 1));
                 float res[4];
                 join_v(ch, cl, res);
 #pragma unroll
@@ -388,33 +459,42 @@ __global__ __launch_bounds__((XT<C, D>::NTH), (XT<C, D>::MINW)) void k_x3_conv(c
                 e16* y = static_cast<e16*>(yout);
                 typename std::conditional<C == 32, e16x8, e16x4>::type oh, ol;
                 split_v(out, oh, ol);
-                *reinterpret_cast<decltype(oh)*>(y + pix * 2 * C + NCH * g) = oh;
-                *reinterpret_cast<decltype(ol)*>(y + pix * 2 * C + C + NCH * g) = ol;
+                if constexpr (BLDS) {
+                    e16* yp = y + (((long)b * H + h) * T + t0) * 2 * C + (unsigned)((c0 + ne) * 2 * C + 4 * ge);
+                    *reinterpret_cast<decltype(oh)*>(yp) = oh;
+                    *reinterpret_cast<decltype(ol)*>(yp + C) = ol;
+                } else {
+                    *reinterpret_cast<decltype(oh)*>(y + pix * 2 * C + NCH * g) = oh;
+                    *reinterpret_cast<decltype(ol)*>(y + pix * 2 * C + C + NCH * g) = ol;
+                }
             }
         }
     }
 }
 
-template <int C, int D, bool PLANAR>
+// what the training modes of k_x3_conv take beyond the block's own arguments (MODE 1: h1; MODE 2: dy, scale)
+struct X3Aux { e16* h1 = nullptr; const e16* dy = nullptr; const float* scale = nullptr; };
+template <int C, int D, bool PLANAR, int MODE = 0>
 int launch_x3(const e16* x, const float* w1, const float* b1, const float* w2, const float* b2, void* y, int B, int H, int T,
-              hipStream_t st) {
+              hipStream_t st, X3Aux aux = X3Aux()) {
     using G = XT<C, D>;
     const int tiles_h = (H + G::TH - 1) / G::TH, tiles_t = (T + G::TW - 1) / G::TW, ntiles = B * tiles_h * tiles_t;
     static AttrOnce once;
-    auto kern = k_x3_conv<C, D, PLANAR>;
-    if (int rc = raise_lds(kern, G::LDS_BYTES, once)) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid_for(ntiles, G::LDS_BYTES, 2)), dim3(G::NTH), G::LDS_BYTES, st, x, w1, b1, w2, b2, y, B, H, T,
-                       tiles_h, tiles_t, ntiles);
+    auto kern = k_x3_conv<C, D, PLANAR, MODE>;
+    constexpr int LDS = G::lds_bytes(MODE);
+    if (int rc = raise_lds(kern, LDS, once)) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid_for(ntiles, LDS, 2)), dim3(G::NTH), LDS, st, x, w1, b1, w2, b2, y, B, H, T,
+                       tiles_h, tiles_t, ntiles, aux.h1, aux.dy, aux.scale);
     TT_LAUNCH_CHECK();
     return 0;
 }
-template <int C, bool PLANAR>
+template <int C, bool PLANAR, int MODE = 0>
 int x3_d(const e16* x, const float* w1, const float* b1, const float* w2, const float* b2, void* y, int B, int H, int T, int d,
-         hipStream_t st) {
+         hipStream_t st, X3Aux aux = X3Aux()) {
     switch (d) {
-        case 1: return launch_x3<C, 1, PLANAR>(x, w1, b1, w2, b2, y, B, H, T, st);
-        case 2: return launch_x3<C, 2, PLANAR>(x, w1, b1, w2, b2, y, B, H, T, st);
-        case 3: return launch_x3<C, 3, PLANAR>(x, w1, b1, w2, b2, y, B, H, T, st);
+        case 1: return launch_x3<C, 1, PLANAR, MODE>(x, w1, b1, w2, b2, y, B, H, T, st, aux);
+        case 2: return launch_x3<C, 2, PLANAR, MODE>(x, w1, b1, w2, b2, y, B, H, T, st, aux);
+        case 3: return launch_x3<C, 3, PLANAR, MODE>(x, w1, b1, w2, b2, y, B, H, T, st, aux);
     }
     return TT_E_UNSUPPORTED;
 }
@@ -1211,6 +1291,453 @@ int launch_latdec(const float* z, int Dz, float fill, const float* w, const floa
     return 0;
 }
 
+// ---- training backward of one residual block on split operands ---------------------------------------------------------------------
+// Saved by the training forward: the block input x and h1 = ELU(W1 (*) x + b1), both x3 tensors.  With the incoming gradient dy:
+//   g2 = dy ELU'(W2 h1 + b2)            dW2 = sum g2 (x) h1      db2 = sum g2                 k_x3_bwd_a (pointwise; K = pixels for dW2)
+//   g1 = (W2^T g2) ELU'(h1)             db1 = sum g1             g1 -> scratch (x3)           k_x3_bwd_a
+//   dx = dy + W1^T (*)_D g1                                                                  k_x3_conv<.., MODE 2>
+//   dW1[co][ci][tap] = sum g1[co][p] x[ci][p + tap]                                          k_x3_wgrad (K = pixels)
+// Every matrix product is the three-term form Ahi Bhi + 2^-11 (Ahi Blo + Alo Bhi) with fp32 accumulators, the cross terms in their own
+// accumulators; bias sums, ELU' and the residual add are fp32.  The weight and bias gradients leave every workgroup as a register dump
+// and k_x3_reduce sums the dumps in a fixed order (no float atomics: the backward is bit-reproducible) into the fp32 gradients (+=).
+//
+// Gradient range.  A (hi, lo) pair is exact to 2^-22 relative only while |v| >~ 2^-15 (below, it holds 2^-35 absolute), and activation
+// gradients of a mean-reduced loss sit at 1e-7 .. 1e-10.  The level's incoming dy is therefore multiplied by a power of two S, chosen on
+// the device (k_x3_absmax + k_x3_scale_fin: no host sync) so that abs-max(dy) S lies in [2^8, 2^9) -- 2^7 of headroom below 65504 for the
+// growth through the blocks of a level; S = 1 for an all-zero or a non-finite dy (the latter comes out non-finite by itself).  Every x3
+// gradient tensor carries S; dx is multiplied by 1 / S where it leaves as fp32 (PLANAR epilogue / tt_x3_unpack_scaled), the weight and
+// bias gradients in the reduce.  Powers of two: exact, S never shows in a result.  scale = {S, 1 / S} in device memory.
+constexpr int XSC_BLOCKS = 1024;                                 // partial maxima of k_x3_absmax
+__global__ __launch_bounds__(NT) void k_x3_absmax(const float* __restrict__ x, long n, unsigned* __restrict__ part) {
+    __shared__ unsigned sm[NT / 64];
+    unsigned m = 0;                                              // |v| as bits: integer order = magnitude order, NaN above inf
+    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n; i += (long)gridDim.x * NT) {
+        const unsigned b = __float_as_uint(x[i]) & 0x7fffffffu;
+        m = b > m ? b : m;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const unsigned q = (unsigned)__shfl_xor((int)m, o, 64); m = q > m ? q : m; }
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < NT / 64; ++w) m = sm[w] > m ? sm[w] : m;
+        part[blockIdx.x] = m;
+    }
+}
+__global__ __launch_bounds__(NT) void k_x3_scale_fin(const unsigned* __restrict__ part, int nb, float* __restrict__ scale) {
+    __shared__ unsigned sm[NT / 64];
+    unsigned m = 0;
+    for (int i = threadIdx.x; i < nb; i += NT) m = part[i] > m ? part[i] : m;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const unsigned q = (unsigned)__shfl_xor((int)m, o, 64); m = q > m ? q : m; }
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < NT / 64; ++w) m = sm[w] > m ? sm[w] : m;
+        int se = 0;                                              // S = 2^se
+        if (m != 0u && m < 0x7f800000u) {
+            const int e = (int)(m >> 23) - 127;                  // abs-max in [2^e, 2^(e+1)) (subnormal: e = -127, clamped below)
+            se = 8 - e;
+            se = se > 120 ? 120 : (se < -120 ? -120 : se);
+        }
+        scale[0] = __uint_as_float((unsigned)(127 + se) << 23);
+        scale[1] = __uint_as_float((unsigned)(127 - se) << 23);
+    }
+}
+
+// ---- pointwise chain: one wave per group of 16 consecutive pixels, operands straight from HBM in B-operand order (the split-operand
+// form of k_wrb_bwd_a, conv_wide_bf16.hip).  Every workgroup leaves ONE dump [dW2: ((a NCT + c) 4 + r) 64 + lane][db1 C][db2 C] (its four
+// waves summed through LDS).  The 16-pixel tiles of g2 and h1 (both planes) are read back transposed (lds_tr16) as the K = pixels operands.
+template <int C> struct XA {
+    static constexpr int PS = C * 2 + 8;                         // bytes per pixel of one transposition buffer (bank spread)
+    static constexpr int WAVE_BYTES = 4 * 16 * PS;               // g2 hi, g2 lo, h1 hi, h1 lo of one group
+    static constexpr int DUMP = C * C + 2 * C;                   // floats per wave
+    static constexpr int LDS_BYTES = 4 * WAVE_BYTES > 16 * DUMP ? 4 * WAVE_BYTES : 16 * DUMP;
+};
+constexpr int X3_MAX_A_WG = 1024, X3_MAX_W_WG = 512;             // workgroups that leave dumps (bounds the scratch)
+
+template <int C>
+__global__ __launch_bounds__(NT) void k_x3_bwd_a(const e16* __restrict__ h1, const e16* __restrict__ dy, const float* __restrict__ w2,
+                                                 const float* __restrict__ b2, e16* __restrict__ g1, float* __restrict__ part, long npix,
+                                                 long ngroups) {
+    using G = XA<C>;
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = lane & 15, g = lane >> 4;
+    constexpr int NCT = C / 16;
+    constexpr int NCH = C == 32 ? 8 : 4;
+    typedef typename std::conditional<C == 32, e16x8, e16x4>::type vec_t;     // a lane's channels of one pixel and plane
+
+    // W2 (rows = output channel) and W2^T (rows = input channel), both planes, rows in the order of chan_of
+    vec_t A2H[NCT], A2L[NCT], ATH[NCT], ATL[NCT];
+#pragma unroll
+    for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            e16 h_, l_;
+            split(w2[chan_of<C>(ct, n) * C + NCH * g + j], h_, l_); A2H[ct][j] = h_; A2L[ct][j] = l_;
+            split(w2[(NCH * g + j) * C + chan_of<C>(ct, n)], h_, l_); ATH[ct][j] = h_; ATL[ct][j] = l_;
+        }
+    auto mm = [&](vec_t a, vec_t b, f32x4 c) {
+        if constexpr (C == 32) return mma32(a, b, c);
+        else return mma16(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c);
+    };
+    float b2r[NCH], db1a[NCH], db2a[NCH];
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) { b2r[j] = b2[NCH * g + j]; db1a[j] = 0.f; db2a[j] = 0.f; }
+    f32x4 dwm[NCT][NCT], dwl[NCT][NCT];                          // dW2: hi x hi, and the two cross terms
+#pragma unroll
+    for (int a = 0; a < NCT; ++a)
+#pragma unroll
+        for (int c = 0; c < NCT; ++c) { dwm[a][c] = f32x4{0.f, 0.f, 0.f, 0.f}; dwl[a][c] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+
+    unsigned char* tb = smem + wave * G::WAVE_BYTES;             // this wave's tiles: g2 hi, g2 lo, h1 hi, h1 lo
+    const int trj = n >> 2, trq = n & 3;                         // transpose read: this lane supplies row trj, columns 4 trq..
+
+    vec_t zero_v;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) zero_v[j] = (e16)0.f;
+    const long gstride = (long)gridDim.x * 4;
+    long grp = (long)blockIdx.x * 4 + wave;
+    vec_t hh = zero_v, hl = zero_v, dh = zero_v, dl = zero_v;
+    if (grp < ngroups && grp * 16 + n < npix) {
+        const long o = (grp * 16 + n) * 2 * C + NCH * g;
+        hh = *reinterpret_cast<const vec_t*>(h1 + o); hl = *reinterpret_cast<const vec_t*>(h1 + o + C);
+        dh = *reinterpret_cast<const vec_t*>(dy + o); dl = *reinterpret_cast<const vec_t*>(dy + o + C);
+    }
+    for (; grp < ngroups; grp += gstride) {
+        const long pix = grp * 16 + n;
+        const bool valid = pix < npix;
+        // the next group's operands are on their way while this one is processed
+        const long pn = (grp + gstride) * 16 + n;
+        vec_t hh_n = zero_v, hl_n = zero_v, dh_n = zero_v, dl_n = zero_v;
+        if (grp + gstride < ngroups && pn < npix) {
+            const long o = pn * 2 * C + NCH * g;
+            hh_n = *reinterpret_cast<const vec_t*>(h1 + o); hl_n = *reinterpret_cast<const vec_t*>(h1 + o + C);
+            dh_n = *reinterpret_cast<const vec_t*>(dy + o); dl_n = *reinterpret_cast<const vec_t*>(dy + o + C);
+        }
+        f32x4 zm[NCT], zl[NCT];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) {
+            zm[ct] = mm(A2H[ct], hh, f32x4{b2r[4 * ct], b2r[4 * ct + 1], b2r[4 * ct + 2], b2r[4 * ct + 3]});
+            zl[ct] = mm(A2H[ct], hl, f32x4{0.f, 0.f, 0.f, 0.f});
+        }
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) zl[ct] = mm(A2L[ct], hh, zl[ct]);
+        float hv[NCH], dv[NCH], gv[NCH], g1v[NCH];
+        join_v(hh, hl, hv);
+        join_v(dh, dl, dv);
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            const float a2 = __builtin_fmaf(zl[j >> 2][j & 3], LO_INV, zm[j >> 2][j & 3]);
+            gv[j] = dv[j] * (a2 > 0.f ? 1.f : __expf(a2));       // ELU'(W2 h1 + b2); invalid pixels: dv = 0
+        }
+        vec_t gh, gl, qh, ql;
+        split_v<true>(gv, gh, gl);
+        f32x4 um[NCT], ul[NCT];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) {
+            um[ct] = mm(ATH[ct], gh, f32x4{0.f, 0.f, 0.f, 0.f});
+            ul[ct] = mm(ATH[ct], gl, f32x4{0.f, 0.f, 0.f, 0.f});
+        }
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) ul[ct] = mm(ATL[ct], gh, ul[ct]);
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            g1v[j] = __builtin_fmaf(ul[j >> 2][j & 3], LO_INV, um[j >> 2][j & 3]) * elu_grad_from_out(hv[j]);
+            db2a[j] += gv[j]; db1a[j] += g1v[j];                 // invalid pixels contribute zeros
+        }
+        split_v(g1v, qh, ql);
+        if (valid) {
+            *reinterpret_cast<vec_t*>(g1 + pix * 2 * C + NCH * g) = qh;
+            *reinterpret_cast<vec_t*>(g1 + pix * 2 * C + C + NCH * g) = ql;
+        }
+        // transposition buffers: pixel n, this lane's channels, in 8-byte pieces
+        {
+            const vec_t src[4] = {gh, gl, hh, hl};
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                unsigned char* d = tb + b * 16 * G::PS + n * G::PS + 2 * NCH * g;
+                if constexpr (C == 32) {
+                    const u32x4 v = __builtin_bit_cast(u32x4, src[b]);
+                    *reinterpret_cast<u32x2*>(d) = u32x2{v.x, v.y};
+                    *reinterpret_cast<u32x2*>(d + 8) = u32x2{v.z, v.w};
+                } else {
+                    *reinterpret_cast<u32x2*>(d) = __builtin_bit_cast(u32x2, src[b]);
+                }
+            }
+        }
+        // dW2[co][ci] += sum over the 16 pixels g2[co][p] h1[ci][p]: the tiles read back transposed
+        // (same wave wrote them: LDS operations of one wave complete in order; the fence only stops the compiler)
+        __builtin_amdgcn_wave_barrier();
+        asm volatile("" ::: "memory");
+        s16x4 gah[NCT], gal[NCT], hbh[NCT], hbl[NCT];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) {
+            const int o = (4 * g + trj) * G::PS + (16 * ct + 4 * trq) * 2;
+            gah[ct] = lds_tr16(tb + o);
+            gal[ct] = lds_tr16(tb + 16 * G::PS + o);
+            hbh[ct] = lds_tr16(tb + 32 * G::PS + o);
+            hbl[ct] = lds_tr16(tb + 48 * G::PS + o);
+        }
+#pragma unroll
+        for (int a = 0; a < NCT; ++a)
+#pragma unroll
+            for (int c = 0; c < NCT; ++c) {
+                dwm[a][c] = mma16(gah[a], hbh[c], dwm[a][c]);
+                dwl[a][c] = mma16(gah[a], hbl[c], dwl[a][c]);
+                dwl[a][c] = mma16(gal[a], hbh[c], dwl[a][c]);
+            }
+        asm volatile("" ::: "memory");
+        hh = hh_n; hl = hl_n; dh = dh_n; dl = dl_n;
+    }
+
+    // ---- register dumps of the four waves, summed in LDS (plain stores, no atomics), one dump per workgroup ----
+    __syncthreads();
+    float* red = reinterpret_cast<float*>(smem) + wave * G::DUMP;
+#pragma unroll
+    for (int a = 0; a < NCT; ++a)
+#pragma unroll
+        for (int c = 0; c < NCT; ++c)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) red[((a * NCT + c) * 4 + r) * 64 + lane] = __builtin_fmaf(dwl[a][c][r], LO_INV, dwm[a][c][r]);
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        float s1 = db1a[j], s2 = db2a[j];
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
+        if (n == 0) { red[C * C + NCH * g + j] = s1; red[C * C + C + NCH * g + j] = s2; }
+    }
+    __syncthreads();
+    const float* all = reinterpret_cast<const float*>(smem);
+    float* pw = part + (long)blockIdx.x * G::DUMP;
+    for (int i = tid; i < G::DUMP; i += NT) pw[i] = (all[i] + all[G::DUMP + i]) + (all[2 * G::DUMP + i] + all[3 * G::DUMP + i]);
+}
+
+// ---- 3x3 weight gradient: dW1[co][ci][tap] = sum_pix g1[co][pix] x[ci][pix + tap], K = pixels, 32 per product -------------------------
+// The split-operand form of k_wrb_wgrad (conv_wide_bf16.hip).  The x tile (with halo) and the g1 tile are x3 LDS images filled by LDS-DMA
+// ([pixel][hi C][lo C]); all four operand planes come out of them by transpose reads (two per operand: pixels 4g..4g+3 and 16+4g..16+4g+3 of
+// the 32-pixel chunk -- the K order is free as long as both operands use the same one).  At C = 32 (128 bytes per pixel) the two 16-channel
+// halves of either plane are swapped in every second PAIR of pixels (a permutation of the DMA sources), which keeps the four pixels a
+// 16-lane group reads on different banks.
+// Wave roles: C = 32: ci-tile w & 1, column half w >> 1;  C = 16: column half w & 1, rows of parity w >> 1.
+// Every wave dumps its accumulators [(tap NA + a) 4 + r][lane]; k_x3_reduce sums the dumps.
+template <int C, int D> struct XW {
+    static constexpr int TH = C == 32 ? 4 : 8, TW = 64;
+    static constexpr int PB = 4 * C, PP = PB / 16;               // bytes / 16-byte pieces per pixel
+    static constexpr int RW = TW + 2 * D, ROWS = TH + 2 * D;
+    static constexpr int XP = ROWS * RW * PP, GP = TH * TW * PP; // 16-byte pieces
+    static constexpr int XPR = (XP + NT - 1) / NT * NT;
+    static constexpr int X_BYTES = XPR * 16, G_BYTES = GP * 16;
+    static constexpr int NA = C / 16;                            // co-tiles a wave accumulates
+    static constexpr int DUMP = 9 * NA * 256;                    // floats per wave
+    static constexpr int LDS_BYTES = X_BYTES + G_BYTES;
+    static_assert(GP % NT == 0, "whole DMA instructions");
+};
+// piece `pc` of image pixel q sits at position pc ^ wswz(q)
+template <int C> __device__ __forceinline__ int wswz(int q) { return C == 32 ? (((q >> 1) & 1) << 1) : 0; }
+
+template <int C, int D>
+__global__ __launch_bounds__(NT) void k_x3_wgrad(const e16* __restrict__ x, const e16* __restrict__ g1, float* __restrict__ part, int B,
+                                                 int H, int T, int tiles_h, int tiles_t, int ntiles) {
+    using G = XW<C, D>;
+    constexpr int PB = G::PB, PP = G::PP, NA = G::NA, CG = C / 8;
+    extern __shared__ __align__(16) unsigned char smem[];
+    unsigned char* xs = smem;
+    unsigned char* gs = smem + G::X_BYTES;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = lane & 15, g = lane >> 4;
+    const int trj = n >> 2, trq = n & 3;
+    const int cit = C == 32 ? (wave & 1) : 0;                    // ci-tile of this wave
+    const int colh = C == 32 ? (wave >> 1) : (wave & 1);         // 32-pixel column half
+    const int row0 = C == 32 ? 0 : (wave >> 1), rstep = C == 32 ? 1 : 2;
+    f32x4 accm[9][NA], accl[9][NA];
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+#pragma unroll
+        for (int a = 0; a < NA; ++a) { accm[k][a] = f32x4{0.f, 0.f, 0.f, 0.f}; accl[k][a] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+
+    // the K = 32 operand (tile `ct` of 16 channels, plane pl) of the chunk whose first-half pixel of this lane is image pixel q0 of `img`
+    auto ldop = [&](const unsigned char* img, int q0, int ct, int pl) {
+        s16x4 h2[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int q = q0 + 16 * u;
+            const int pc = pl * CG + 2 * ct + (trq >> 1);
+            h2[u] = lds_tr16(img + (long)q * PB + 16 * (pc ^ wswz<C>(q)) + 8 * (trq & 1));
+        }
+        return __builtin_bit_cast(e16x8, __builtin_shufflevector(h2[0], h2[1], 0, 1, 2, 3, 4, 5, 6, 7));
+    };
+
+    const e16* zero = reinterpret_cast<const e16*>(&g_wzero16);
+    for (int v = blockIdx.x; v < ntiles; v += gridDim.x) {
+        int tile = xcd_order(v, ntiles);
+        const int tt = tile % tiles_t; tile /= tiles_t;
+        const int th = tile % tiles_h;
+        const int b = tile / tiles_h, h0 = th * G::TH, t0 = tt * G::TW;
+        const unsigned char* xb = reinterpret_cast<const unsigned char*>(x) + (long)b * H * T * PB;
+        const unsigned char* gb = reinterpret_cast<const unsigned char*>(g1) + (long)b * H * T * PB;
+        __syncthreads();
+        for (int i = wave * 64; i < G::XPR; i += NT) {
+            const int p = i + lane, q = p / PP, pc = (p - q * PP) ^ wswz<C>(q);
+            const int row = q / G::RW, px = q - row * G::RW;
+            const int h = h0 - D + row, t = t0 - D + px;
+            const bool ok = p < G::XP && (unsigned)h < (unsigned)H && (unsigned)t < (unsigned)T;
+            glds16(ok ? (const void*)(xb + ((long)h * T + t) * PB + pc * 16) : (const void*)zero, xs + (long)i * 16);
+        }
+        for (int i = wave * 64; i < G::GP; i += NT) {
+            const int p = i + lane, q = p / PP, pc = (p - q * PP) ^ wswz<C>(q);
+            const int row = q / G::TW, px = q - row * G::TW;
+            const int h = h0 + row, t = t0 + px;
+            const bool ok = h < H && t < T;
+            glds16(ok ? (const void*)(gb + ((long)h * T + t) * PB + pc * 16) : (const void*)zero, gs + (long)i * 16);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+
+        const int c0 = colh * 32 + 4 * g + trj;                  // first-half pixel whose address this lane supplies
+        for (int r = row0; r < G::TH; r += rstep) {
+            if (h0 + r >= H) break;
+            e16x8 gah[NA], gal[NA];
+#pragma unroll
+            for (int a = 0; a < NA; ++a) { gah[a] = ldop(gs, r * G::TW + c0, a, 0); gal[a] = ldop(gs, r * G::TW + c0, a, 1); }
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                const int kh = k / 3, kw = k - 3 * kh;
+                const int q0 = (r + kh * D) * G::RW + c0 + kw * D;
+                const e16x8 xh = ldop(xs, q0, cit, 0), xl = ldop(xs, q0, cit, 1);
+#pragma unroll
+                for (int a = 0; a < NA; ++a) {
+                    accm[k][a] = mma32(gah[a], xh, accm[k][a]);
+                    accl[k][a] = mma32(gah[a], xl, accl[k][a]);
+                    accl[k][a] = mma32(gal[a], xh, accl[k][a]);
+                }
+            }
+        }
+    }
+
+    float* pw = part + ((long)blockIdx.x * 4 + wave) * G::DUMP;
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+#pragma unroll
+        for (int a = 0; a < NA; ++a)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) pw[((k * NA + a) * 4 + r) * 64 + lane] = __builtin_fmaf(accl[k][a][r], LO_INV, accm[k][a][r]);
+}
+
+// ---- sum of the dumps into the fp32 gradients (+=), multiplied by 1 / S = scale[1] (device memory) ------------------------------------
+// The shape of k_wrb_reduce (wide_common.h): 1024 threads = REL consecutive dump elements x RSL slices of the contributors, every slice
+// and the final sum over slices in a fixed order.
+template <int C>
+__global__ __launch_bounds__(1024) void k_x3_reduce(const float* __restrict__ pw, int gw, const float* __restrict__ pa, int ga,
+                                                    float* __restrict__ dw1, float* __restrict__ db1, float* __restrict__ dw2,
+                                                    float* __restrict__ db2, const float* __restrict__ scale) {
+    constexpr int NCT = C / 16;
+    constexpr int WDUMP = 9 * NCT * 256, NEW = NCT * WDUMP;      // wgrad: elements = (wave role) x dump
+    constexpr int ADUMP = C * C + 2 * C;
+    __shared__ float red[RSL][REL];
+    const int el = threadIdx.x % REL, sl = threadIdx.x / REL;
+    const int e = blockIdx.x * REL + el;
+    float sum = 0.f;
+    float* dst = nullptr;
+    if (e < NEW) {
+        const int role = e / WDUMP, rest = e - role * WDUMP;     // C = 32: role = ci-tile = wave & 1;  C = 16: one role
+        const int k = rest / (NCT * 256), a = (rest >> 8) % NCT, r = (rest >> 6) & 3, lane = rest & 63;
+        constexpr int NS = 4 / NCT;                              // waves per workgroup that contribute to this element
+        const int ncontrib = gw * NS;
+        for (int j = sl; j < ncontrib; j += RSL) {
+            const int wg = j / NS, s = j - wg * NS;
+            const int wave = C == 32 ? role + 2 * s : s;
+            sum += pw[((long)wg * 4 + wave) * WDUMP + rest];
+        }
+        const int co = 16 * a + 4 * (lane >> 4) + r, ci = 16 * role + (lane & 15);
+        dst = dw1 + (co * C + ci) * 9 + k;
+    } else if (e < NEW + ADUMP) {
+        const int q = e - NEW;
+        for (int j = sl; j < ga; j += RSL) sum += pa[(long)j * ADUMP + q];
+        if (q < C * C) {
+            const int a = q / (NCT * 256), c = (q >> 8) % NCT, r = (q >> 6) & 3, lane = q & 63;
+            dst = dw2 + (16 * a + 4 * (lane >> 4) + r) * C + 16 * c + (lane & 15);
+        } else if (q < C * C + C) dst = db1 + (q - C * C);
+        else dst = db2 + (q - C * C - C);
+    }
+    red[sl][el] = sum;
+    __syncthreads();
+    if (sl == 0 && dst) {
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < RSL; ++i) s += red[i][el];
+        *dst += s * scale[1];
+    }
+}
+
+inline int64_t x3_round256(int64_t v) { return (v + 255) / 256 * 256; }
+// Scratch of one block's backward: [g1 x3][bwd_a dumps][wgrad dumps].  The dump regions are sized by the workgroups the SHAPE can employ
+// (a group of 64 pixels / a tile each), capped at X3_MAX_*_WG -- not by the grid of the moment: tt_set_cu_limit may change between the
+// caller's size query and the launch, and a region sized for fewer workgroups than are launched would be written out of bounds.
+template <int C> struct XBW {
+    static int a_wgs(int B, int H, int T) {
+        const long want = (((long)B * H * T + 15) / 16 + 3) / 4;
+        return (int)(want < X3_MAX_A_WG ? want : X3_MAX_A_WG);
+    }
+    static int w_wgs(int B, int H, int T) {
+        using G = XW<C, 1>;                                      // the tile is the same at every dilation
+        const long want = (long)B * ((H + G::TH - 1) / G::TH) * ((T + G::TW - 1) / G::TW);
+        return (int)(want < X3_MAX_W_WG ? want : X3_MAX_W_WG);
+    }
+    static int64_t a_bytes(int B, int H, int T) { return x3_round256((int64_t)a_wgs(B, H, T) * XA<C>::DUMP * 4); }
+    static int64_t w_bytes(int B, int H, int T) { return (int64_t)w_wgs(B, H, T) * 4 * (9 * (C / 16) * 256) * 4; }
+};
+
+template <int C, int D>
+int launch_x3_wgrad(const e16* x, const e16* g1, float* part, int B, int H, int T, int& gw, hipStream_t st) {
+    using G = XW<C, D>;
+    const int tiles_h = (H + G::TH - 1) / G::TH, tiles_t = (T + G::TW - 1) / G::TW, ntiles = B * tiles_h * tiles_t;
+    static AttrOnce once;
+    auto kern = k_x3_wgrad<C, D>;
+    if (int rc = raise_lds(kern, G::LDS_BYTES, once)) return rc;
+    gw = grid_for(ntiles, G::LDS_BYTES, 1);
+    if (gw > XBW<C>::w_wgs(B, H, T)) gw = XBW<C>::w_wgs(B, H, T);
+    hipLaunchKernelGGL(kern, dim3(gw), dim3(NT), G::LDS_BYTES, st, x, g1, part, B, H, T, tiles_h, tiles_t, ntiles);
+    TT_LAUNCH_CHECK();
+    return 0;
+}
+
+template <int C>
+int x3_block_bwd(const e16* x, const e16* h1, const e16* dy, const float* w1, const float* w2, const float* b2, void* dx, bool planar,
+                 float* dw1, float* db1, float* dw2, float* db2, const float* scale, unsigned char* ws, int B, int H, int T, int d,
+                 hipStream_t st) {
+    const long npix = (long)B * H * T, ngroups = (npix + 15) / 16;
+    e16* g1 = reinterpret_cast<e16*>(ws);
+    float* pa = reinterpret_cast<float*>(ws + x3_round256(npix * 4 * C));
+    float* pw = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(pa) + XBW<C>::a_bytes(B, H, T));
+    // pointwise chain: g1, and the dumps of dW2 / db1 / db2
+    const long want = XBW<C>::a_wgs(B, H, T), cap = (long)tt_cus() * 8;
+    const int ga = (int)(want < cap ? want : cap);
+    hipLaunchKernelGGL(k_x3_bwd_a<C>, dim3(ga), dim3(NT), XA<C>::LDS_BYTES, st, h1, dy, w2, b2, g1, pa, npix, ngroups);
+    TT_LAUNCH_CHECK();
+    // data gradient
+    X3Aux aux;
+    aux.dy = dy; aux.scale = scale;
+    if (dx)                                                      // dx = NULL: the level's input wants no gradient
+        if (int rc = planar ? x3_d<C, true, 2>(g1, w1, nullptr, nullptr, nullptr, dx, B, H, T, d, st, aux)
+                            : x3_d<C, false, 2>(g1, w1, nullptr, nullptr, nullptr, dx, B, H, T, d, st, aux)) return rc;
+    // 3x3 weight gradient
+    int gw = 0, rc = TT_E_UNSUPPORTED;
+    switch (d) {
+        case 1: rc = launch_x3_wgrad<C, 1>(x, g1, pw, B, H, T, gw, st); break;
+        case 2: rc = launch_x3_wgrad<C, 2>(x, g1, pw, B, H, T, gw, st); break;
+        case 3: rc = launch_x3_wgrad<C, 3>(x, g1, pw, B, H, T, gw, st); break;
+    }
+    if (rc) return rc;
+    constexpr int TOTAL = (C / 16) * 9 * (C / 16) * 256 + C * C + 2 * C;
+    hipLaunchKernelGGL(k_x3_reduce<C>, dim3((TOTAL + REL - 1) / REL), dim3(1024), 0, st, pw, gw, pa, ga, dw1, db1, dw2, db2, scale);
+    TT_LAUNCH_CHECK();
+    return 0;
+}
+
 int x3_block(const e16* x, const float* w1, const float* b1, const float* w2, const float* b2, void* y, bool planar, int B, int C,
              int H, int T, int d, hipStream_t st) {
     if (C == 16) return planar ? x3_d<16, true>(x, w1, b1, w2, b2, y, B, H, T, d, st) : x3_d<16, false>(x, w1, b1, w2, b2, y, B, H, T, d, st);
@@ -1228,34 +1755,88 @@ int64_t tt_x3_bytes(int B, int C, int H, int T) {
     return (int64_t)B * H * T * C * 4;
 }
 
-int tt_x3_pack(const float* x, void* out, int B, int C, int H, int T, void* stream) {
+int tt_x3_pack_scaled(const float* x, void* out, const float* scale, int B, int C, int H, int T, void* stream) {
     if (!x || !out || !x3_layout_ok(B, C, H, T)) return TT_E_BADARG;
     const long npix = (long)B * H * T, pieces = npix * C / 8;
     const unsigned grid = (unsigned)((pieces + NT - 1) / NT);
     hipStream_t st = tt_stream(stream);
-    if (C == 16) hipLaunchKernelGGL(k_x3_pack<16>, dim3(grid), dim3(NT), 0, st, x, (e16*)out, H, T, npix);
-    else if (C == 64) hipLaunchKernelGGL(k_x3_pack<64>, dim3(grid), dim3(NT), 0, st, x, (e16*)out, H, T, npix);
-    else hipLaunchKernelGGL(k_x3_pack<32>, dim3(grid), dim3(NT), 0, st, x, (e16*)out, H, T, npix);
+    if (C == 16) hipLaunchKernelGGL(k_x3_pack<16>, dim3(grid), dim3(NT), 0, st, x, (e16*)out, H, T, npix, scale);
+    else if (C == 64) hipLaunchKernelGGL(k_x3_pack<64>, dim3(grid), dim3(NT), 0, st, x, (e16*)out, H, T, npix, scale);
+    else hipLaunchKernelGGL(k_x3_pack<32>, dim3(grid), dim3(NT), 0, st, x, (e16*)out, H, T, npix, scale);
+    TT_LAUNCH_CHECK();
+    return 0;
+}
+
+int tt_x3_pack(const float* x, void* out, int B, int C, int H, int T, void* stream) {
+    return tt_x3_pack_scaled(x, out, nullptr, B, C, H, T, stream);
+}
+
+int tt_x3_unpack_scaled(const void* in, float* y, const float* scale, int B, int C, int H, int T, void* stream) {
+    if (!in || !y || !x3_layout_ok(B, C, H, T)) return TT_E_BADARG;
+    const long npix = (long)B * H * T, pieces = npix * C / 8;
+    const unsigned grid = (unsigned)((pieces + NT - 1) / NT);
+    hipStream_t st = tt_stream(stream);
+    if (C == 16) hipLaunchKernelGGL(k_x3_unpack<16>, dim3(grid), dim3(NT), 0, st, (const e16*)in, y, H, T, npix, scale);
+    else if (C == 64) hipLaunchKernelGGL(k_x3_unpack<64>, dim3(grid), dim3(NT), 0, st, (const e16*)in, y, H, T, npix, scale);
+    else hipLaunchKernelGGL(k_x3_unpack<32>, dim3(grid), dim3(NT), 0, st, (const e16*)in, y, H, T, npix, scale);
     TT_LAUNCH_CHECK();
     return 0;
 }
 
 int tt_x3_unpack(const void* in, float* y, int B, int C, int H, int T, void* stream) {
-    if (!in || !y || !x3_layout_ok(B, C, H, T)) return TT_E_BADARG;
-    const long npix = (long)B * H * T, pieces = npix * C / 8;
-    const unsigned grid = (unsigned)((pieces + NT - 1) / NT);
-    hipStream_t st = tt_stream(stream);
-    if (C == 16) hipLaunchKernelGGL(k_x3_unpack<16>, dim3(grid), dim3(NT), 0, st, (const e16*)in, y, H, T, npix);
-    else if (C == 64) hipLaunchKernelGGL(k_x3_unpack<64>, dim3(grid), dim3(NT), 0, st, (const e16*)in, y, H, T, npix);
-    else hipLaunchKernelGGL(k_x3_unpack<32>, dim3(grid), dim3(NT), 0, st, (const e16*)in, y, H, T, npix);
-    TT_LAUNCH_CHECK();
-    return 0;
+    return tt_x3_unpack_scaled(in, y, nullptr, B, C, H, T, stream);
 }
 
 int tt_x3_rb_fwd(const void* x, const float* w1, const float* b1, const float* w2, const float* b2, void* y, int planar_out, int B,
                  int C, int H, int T, int dilation, void* stream) {
     if (!x || !w1 || !b1 || !w2 || !b2 || !y || x == y || !x3_shape_ok(B, C, H, T)) return TT_E_BADARG;
     return x3_block((const e16*)x, w1, b1, w2, b2, y, planar_out != 0, B, C, H, T, dilation, tt_stream(stream));
+}
+
+int tt_x3_rb_fwd_train(const void* x, const float* w1, const float* b1, const float* w2, const float* b2, void* y, int planar_out, void* h1,
+                       int B, int C, int H, int T, int dilation, void* stream) {
+    if (!x || !w1 || !b1 || !w2 || !b2 || !y || !h1 || x == y || x == h1 || y == h1 || !x3_shape_ok(B, C, H, T)) return TT_E_BADARG;
+    hipStream_t st = tt_stream(stream);
+    X3Aux aux;
+    aux.h1 = static_cast<e16*>(h1);
+    const e16* xe = static_cast<const e16*>(x);
+    if (C == 16) return planar_out ? x3_d<16, true, 1>(xe, w1, b1, w2, b2, y, B, H, T, dilation, st, aux)
+                                   : x3_d<16, false, 1>(xe, w1, b1, w2, b2, y, B, H, T, dilation, st, aux);
+    return planar_out ? x3_d<32, true, 1>(xe, w1, b1, w2, b2, y, B, H, T, dilation, st, aux)
+                      : x3_d<32, false, 1>(xe, w1, b1, w2, b2, y, B, H, T, dilation, st, aux);
+}
+
+int64_t tt_x3_grad_scale_scratch_bytes(void) { return (int64_t)XSC_BLOCKS * 4; }
+
+int tt_x3_grad_scale(const float* dy, int64_t n, float* scale, void* ws, void* stream) {
+    if (!dy || !scale || !ws || n < 1) return TT_E_BADARG;
+    hipStream_t st = tt_stream(stream);
+    const int64_t want = (n + NT - 1) / NT;
+    const int nb = (int)(want < XSC_BLOCKS ? want : XSC_BLOCKS);
+    hipLaunchKernelGGL(k_x3_absmax, dim3(nb), dim3(NT), 0, st, dy, (long)n, static_cast<unsigned*>(ws));
+    TT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_x3_scale_fin, dim3(1), dim3(NT), 0, st, static_cast<const unsigned*>(ws), nb, scale);
+    TT_LAUNCH_CHECK();
+    return 0;
+}
+
+int64_t tt_x3_rb_bwd_scratch_bytes(int B, int C, int H, int T) {
+    if (!x3_shape_ok(B, C, H, T)) return -1;
+    const int64_t g1 = x3_round256((int64_t)B * H * T * C * 4);
+    return C == 16 ? g1 + XBW<16>::a_bytes(B, H, T) + XBW<16>::w_bytes(B, H, T) : g1 + XBW<32>::a_bytes(B, H, T) + XBW<32>::w_bytes(B, H, T);
+}
+
+int tt_x3_rb_bwd(const void* x, const void* h1, const void* dy, const float* w1, const float* w2, const float* b2, void* dx, int planar_dx,
+                 float* dw1, float* db1, float* dw2, float* db2, const float* scale, void* ws, int B, int C, int H, int T, int dilation,
+                 void* stream) {
+    if (!x || !h1 || !dy || !w1 || !w2 || !b2 || !dw1 || !db1 || !dw2 || !db2 || !scale || !ws || (dx && (dx == dy || dx == x || dx == h1)) ||
+        !x3_shape_ok(B, C, H, T) || (int64_t)B * H * T >= ((int64_t)1 << 34) || dilation < 1 || dilation > 3)
+        return TT_E_BADARG;
+    hipStream_t st = tt_stream(stream);
+    const e16 *xe = static_cast<const e16*>(x), *he = static_cast<const e16*>(h1), *de = static_cast<const e16*>(dy);
+    unsigned char* w = static_cast<unsigned char*>(ws);
+    if (C == 16) return x3_block_bwd<16>(xe, he, de, w1, w2, b2, dx, planar_dx != 0, dw1, db1, dw2, db2, scale, w, B, H, T, dilation, st);
+    return x3_block_bwd<32>(xe, he, de, w1, w2, b2, dx, planar_dx != 0, dw1, db1, dw2, db2, scale, w, B, H, T, dilation, st);
 }
 
 int tt_x3_level_fwd(int nblocks, const void* x, int x3_in, void* y, int x3_out, const float* const* w1, const float* const* b1,

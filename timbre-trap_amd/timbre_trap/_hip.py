@@ -87,6 +87,13 @@ _PROTOS = {
     'tt_x3_unpack': (c_int, [P, P, I, I, I, I, P]),
     'tt_x3_rb_fwd': (c_int, [P, P, P, P, P, P, I, I, I, I, I, I, P]),
     'tt_x3_level_fwd': (c_int, [I, P, I, P, I, P, P, P, P, P, P, I, I, I, I, P]),
+    'tt_x3_rb_fwd_train': (c_int, [P, P, P, P, P, P, I, P, I, I, I, I, I, P]),
+    'tt_x3_grad_scale_scratch_bytes': (c_int64, []),
+    'tt_x3_grad_scale': (c_int, [P, c_int64, P, P, P]),
+    'tt_x3_pack_scaled': (c_int, [P, P, P, I, I, I, I, P]),
+    'tt_x3_unpack_scaled': (c_int, [P, P, P, I, I, I, I, P]),
+    'tt_x3_rb_bwd_scratch_bytes': (c_int64, [I, I, I, I]),
+    'tt_x3_rb_bwd': (c_int, [P, P, P, P, P, P, P, I, P, P, P, P, P, P, I, I, I, I, I, P]),
     'tt_x3n_level_scratch_bytes': (c_int64, [I, I, I, I]),
     'tt_x3n_rb_fwd': (c_int, [P, I, P, P, P, P, P, I, I, I, I, I, I, P]),
     'tt_x3n_level_fwd': (c_int, [I, P, P, P, P, P, P, P, P, I, I, I, I, P]),

@@ -55,6 +55,10 @@ SKIP_FOLD = os.environ.get('TTRAP_SKIP_FOLD', '1') != '0'
 X3_INFER = os.environ.get('TTRAP_X3_INFER', '1') != '0'
 # TTRAP_X3N_INFER=0: the narrow levels stay on the exact-fp32 kernels (A/B, bench.py)
 X3N_INFER = os.environ.get('TTRAP_X3N_INFER', '1') != '0'
+# TTRAP_X3_TRAIN=1 (default off): in fp32 mode the wide levels TRAIN on split fp16 operands too -- forward with saved x3 activations and a
+# split-operand backward (x3.X3LevelTrainFn): fp32-class gradients without the fp32 matrix instructions.  Values beyond +-65504 come out
+# non-finite and there is no fp32 fallback under grad (it would take a host sync per level): check the loss for finiteness.
+X3_TRAIN = os.environ.get('TTRAP_X3_TRAIN', '0') == '1'
 # TTRAP_LOSS_FUSED=0: the squared-error losses compute their gradients in backward from the saved operands (A/B)
 LOSS_FUSED = os.environ.get('TTRAP_LOSS_FUSED', '1') != '0'
 
@@ -62,6 +66,9 @@ FUSED_CHANNELS = (4, 8, 16, 32)
 WIDE_CHANNELS = (4, 8, 16, 32)        # every level of the model (C = 4 needs an even number of frames)
 CL16_CHANNELS = (4, 8, 16, 32, 64)
 X3_CHANNELS = (16, 32)
+# widths on the X3_TRAIN route: those whose level (forward + backward) is faster than the fp32 kernels by more than the round-to-round spread
+# (tools/kb_x3_train.py, profiles/kb_x3_train.txt: C = 32 1.70x, C = 16 1.18x)
+X3_TRAIN_CHANNELS = (16, 32)
 X3N_CHANNELS = (4, 8)                 # the narrow levels: lane-per-pixel split-operand blocks (tt_x3n_level_fwd), fp32 planar in and out
 X3_LATENT_SHAPES = ((64, 128), (32, 32))          # (channels of the top embedding, latent size) with split-operand latent heads
 X3_SHAPES = {}                        # event key -> (B, C, H, T) of the last instrumented call (bench.py's roofline_x3_fwd)
@@ -119,8 +126,9 @@ from .cl16 import (ConvIn16Fn, ConvIn16x1Fn, ConvOut16Fn, ConvOut16PairFn, ConvO
                    ToPlanar32Fn, _as_cl16, _cl16_ok, _pack, _unpack, gate_link, is_cl16, new_cl16)
 from .skip import Add16Fn, Scale16Fn, SkipJoin, SkipJoin16Fn, _join_backward, _riding_join, flush_pending  # noqa: E402,F401
 from .level16 import LatDec16Fn, LatEnc16Fn, Level16Fn, Level16JoinFn, SConv16Fn, TConv16Fn, WideLevelFn  # noqa: E402,F401
-from .x3 import (_x3_blocks_ok, _x3_size_ok, from_x3, is_x3, x3_chain, x3_chain_scope, x3_disabled, x3_inference, x3_latent_decode,  # noqa: E402,F401
-                 x3_latent_encode, x3_latent_ok, x3_level, x3_range_ok, x3_strided_conv, x3_transposed_conv, x3_vouched, x3_vouched_scope, x3n_level)
+from .x3 import (X3LevelTrainFn, _x3_blocks_ok, _x3_size_ok, from_x3, is_x3, x3_chain, x3_chain_scope, x3_disabled, x3_inference,  # noqa: E402,F401
+                 x3_latent_decode, x3_latent_encode, x3_latent_ok, x3_level, x3_level_train, x3_range_ok, x3_strided_conv, x3_training,
+                 x3_transposed_conv, x3_vouched, x3_vouched_scope, x3n_level)
 from .losses import Activations1Fn, ActivationsFn, SqDiff2Fn, SqDiffLossFn, TranscriptionLossFn, decibels, magnitude  # noqa: E402,F401
 
 
@@ -345,6 +353,8 @@ def residual_level(x, blocks, out_x3=False, link=None, join=None):
             return y
         with x3_disabled():
             return residual_level(x, blocks)
+    if x3_training(x, blocks):
+        return x3_level_train(x, blocks)                         # opt-in (X3_TRAIN): split operands forward AND backward
     for b in blocks:
         x = b(x)
     return x

@@ -1,4 +1,5 @@
-"""fp32-class inference on split fp16 operands ("x3", csrc/conv_x3.hip): the thread-local scopes that select it and the no-grad launchers.
+"""fp32-class inference on split fp16 operands ("x3", csrc/conv_x3.hip): the thread-local scopes that select it and the no-grad launchers;
+and, at the end, the opt-in split-operand TRAINING of the wide levels (X3LevelTrainFn, ops.X3_TRAIN).
 Without autocast and without grad (evaluate.py:94-95, transcribe() / reconstruct()) the wide levels do not need the hidden
 activations the fp32 backward reads, and the fp32 matrix instructions are what bounds tt_resblock_fwd: the level then runs on
 (hi, lo) fp16 pairs -- fp32-level results (tests/test_gpu_x3.py: 2e-6 of the tensor's scale against float64) at the 16-bit matrix
@@ -12,7 +13,7 @@ import torch
 from .. import ops as _ops
 from ... import _hip
 from ..._hip import check, ptr, stream_ptr
-from ._common import _f32c
+from ._common import _f32c, _grad_target
 
 _X3_LOCAL = threading.local()
 
@@ -257,3 +258,94 @@ def x3_latent_decode(z, w, b, fill, out_x3):
         check(lib.tt_x3_latent_decode(ptr(z), Dz, float(fill) if fill is not None else 0.0, ptr(w), ptr(b), ptr(y), int(not out_x3), ptr(ws),
                                       B, C, E, D, T, stream_ptr()), 'tt_x3_latent_decode')
     return y
+
+
+# ---- split-operand training of the wide levels (ops.X3_TRAIN) --------------------------------------------------------------------------
+
+def x3_training(x, blocks):
+    """ops.residual_level's test for the X3LevelTrainFn route: the switch, fp32 mode with fp32 storage, grad enabled and wanted by the input
+    or a parameter, a width of ops.X3_TRAIN_CHANNELS, blocks and sizes the kernels take."""
+    if not (_ops.X3_TRAIN and torch.is_grad_enabled() and _ops.precision() == 'fp32' and _ops.wide_storage() == 'fp32'):
+        return False
+    if not (x.dim() == 4 and x.is_cuda and x.dtype == torch.float32):
+        return False
+    C = x.size(1)
+    if not (C in _ops.X3_CHANNELS and C in _ops.X3_TRAIN_CHANNELS and _x3_blocks_ok(C, blocks) and _x3_size_ok(x.size(0), x.size(2), x.size(3))):
+        return False
+    return x.requires_grad or any(p.requires_grad for b in blocks for p in (b.conv1[0].weight, b.conv1[0].bias, b.conv2[0].weight, b.conv2[0].bias))
+
+
+class X3LevelTrainFn(torch.autograd.Function):
+    """
+    block_n(...block1(x)) of a wide level (C = 16, 32) with split operands in BOTH directions (csrc/conv_x3.hip, "training"): fp32 planar
+    (B,C,H,T) in and out; inside, every activation -- and what is saved for backward: each block's input and hidden activation, as many
+    bytes as the fp32 path saves -- is an x3 tensor.  The backward scales the incoming gradient by a power of two chosen on the device
+    (tt_x3_grad_scale: no host sync), runs tt_x3_rb_bwd per block from the last to the first, and returns true (unscaled) gradients.
+    Values beyond +-65504 come out non-finite (no fp32 fallback here: the caller's finite check on the loss catches it).
+    Not @instrumented: its launches are timed one by one under 'x3_rb_{fwd,bwd}_train_C<C>'.
+    """
+
+    @staticmethod
+    def forward(ctx, x, dilations, *params):
+        x = _f32c(x)
+        B, C, H, T = x.shape
+        lib, st = _hip.lib(), stream_ptr()
+        n = len(dilations)
+        ps = [_f32c(p.detach()) for p in params]
+        _hip.require_cuda(x, ps[0])
+        new = lambda: torch.empty((B, H, T, 2, C), dtype=torch.float16, device=x.device)
+        xs, hs = [new()], []
+        check(lib.tt_x3_pack(ptr(x), ptr(xs[0]), B, C, H, T, st), 'tt_x3_pack')
+        y = torch.empty_like(x)
+        for i in range(n):
+            last = i == n - 1
+            w1, b1, w2, b2 = ps[4 * i:4 * i + 4]
+            dst = y if last else new()
+            h1 = new()
+            with _hip.timed('x3_rb_fwd_train_C%d' % C):
+                check(lib.tt_x3_rb_fwd_train(ptr(xs[i]), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(dst), int(last), ptr(h1), B, C, H, T,
+                                             dilations[i], st), 'tt_x3_rb_fwd_train')
+            hs.append(h1)
+            if not last:
+                xs.append(dst)
+        ctx.dilations, ctx.params, ctx.n = tuple(dilations), params, n
+        ctx.save_for_backward(*xs, *hs, *ps)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        n = ctx.n
+        saved = ctx.saved_tensors
+        xs, hs, ps = saved[:n], saved[n:2 * n], saved[2 * n:]
+        dy = _f32c(dy)
+        B, C, H, T = dy.shape
+        lib, st = _hip.lib(), stream_ptr()
+        dev = dy.device
+        scale = torch.empty(2, dtype=torch.float32, device=dev)
+        sws = torch.empty(lib.tt_x3_grad_scale_scratch_bytes(), dtype=torch.uint8, device=dev)
+        check(lib.tt_x3_grad_scale(ptr(dy), dy.numel(), ptr(scale), ptr(sws), st), 'tt_x3_grad_scale')
+        new = lambda: torch.empty((B, H, T, 2, C), dtype=torch.float16, device=dev)
+        cur = new()
+        check(lib.tt_x3_pack_scaled(ptr(dy), ptr(cur), ptr(scale), B, C, H, T, st), 'tt_x3_pack_scaled')
+        other = new() if n > 1 else None
+        dx = torch.empty((B, C, H, T), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        ws = torch.empty(lib.tt_x3_rb_bwd_scratch_bytes(B, C, H, T), dtype=torch.uint8, device=dev)
+        targets = [_grad_target(p) for p in ctx.params]
+        for i in reversed(range(n)):
+            first = i == 0
+            w1, _, w2, b2 = ps[4 * i:4 * i + 4]
+            (dw1, _), (db1, _), (dw2, _), (db2, _) = targets[4 * i:4 * i + 4]
+            dst = dx if first else other
+            with _hip.timed('x3_rb_bwd_train_C%d' % C):
+                check(lib.tt_x3_rb_bwd(ptr(xs[i]), ptr(hs[i]), ptr(cur), ptr(w1), ptr(w2), ptr(b2), ptr(dst), int(first), ptr(dw1), ptr(db1),
+                                       ptr(dw2), ptr(db2), ptr(scale), ptr(ws), B, C, H, T, ctx.dilations[i], st), 'tt_x3_rb_bwd')
+            if not first:
+                cur, other = dst, cur
+        return (dx, None) + tuple(r for _, r in targets)
+
+
+def x3_level_train(x, blocks):
+    params = []
+    for b in blocks:
+        params += [b.conv1[0].weight, b.conv1[0].bias, b.conv2[0].weight, b.conv2[0].bias]
+    return X3LevelTrainFn.apply(x, tuple(b.dilation for b in blocks), *params)
