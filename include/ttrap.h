@@ -103,7 +103,8 @@ int tt_cqt_forward_mag(const tt_cqt_plan* plan, const float* audio, float* out, 
 
 /* coeffs (B, 2, F, n_blocks*1024) [or interleaved complex (B,1,F,T) if in_complex] ->
  * audio (B, 1, n_blocks*66150).  normalize != 0 applies cqtwrapper.py:209-211
- * (divide the whole tensor by its abs-max when that is non-zero) with no host round trip. */
+ * (divide the whole tensor by its abs-max when that is non-zero) with no host round trip.  The abs-max propagates non-finite
+ * values as torch's max does: a NaN sample in any clip makes it NaN and the whole batch comes out NaN, an infinite one divides by inf. */
 int tt_cqt_inverse(const tt_cqt_plan* plan, const float* coeffs, float* audio, void* scratch,
                    int B, int n_blocks, int in_complex, int normalize, void* stream);
 
@@ -116,7 +117,8 @@ int tt_cqt_inverse(const tt_cqt_plan* plan, const float* coeffs, float* audio, v
  *   bfilt   [P]    float2  DFT_P of the wrapped conjugate chirp, divided by P
  *   twP     [P/2]  float2  exp(-2 pi i q / P)          twM [M/2] float2  exp(-2 pi i q / M)
  *   pos_bin [sumL] int32   bin of every ragged window position
- * Same layouts, flags and normalisation rule as tt_cqt_forward / tt_cqt_inverse. */
+ * Same layouts, flags and normalisation rule as tt_cqt_forward / tt_cqt_inverse (non-finite samples under normalize included: a NaN
+ * anywhere in the batch is the peak). */
 typedef struct {
     const float*   chirp;
     const float*   bfilt;

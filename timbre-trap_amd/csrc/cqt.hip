@@ -161,7 +161,9 @@ __global__ __launch_bounds__(FFT_ROWS_THREADS) void k_fft675_rows(const float2* 
 //   Z[e+7f] = sum_b W_7^(b f) G[b][e]                          (thread = (column, e): 7 inputs -> 7 outputs)
 // MODE 0: real-FFT split -> X[q][0..NC] (half spectrum of the 66150 real samples).
 // MODE 1: inverse tail  -> out[q][k] = conj(Z[k]) / NC  written as audio pairs; the workgroup's abs-max goes to *mx
-//         (CQT.decode's inf-norm, reference cqtwrapper.py:209-211) with one atomic per workgroup.
+//         (CQT.decode's inf-norm, reference cqtwrapper.py:209-211) with one atomic per workgroup.  The maximum is taken on the bit
+//         patterns of |v|: non-negative floats order like their bits and a NaN (sign cleared) lies above +inf, so a NaN sample
+//         becomes the peak, as in torch's max, where fmaxf would drop it.
 constexpr int CT = 16;                      // low columns per tile
 constexpr int NTILES = (337 + CT - 1) / CT; // k1 = 1..337 are "low", 338..674 their mirrors
 
@@ -182,7 +184,7 @@ __global__ __launch_bounds__(256) void k_fft49_cols(const float2* __restrict__ A
     __shared__ float2 Al[N2][2 * CT + 1];
     __shared__ float2 Zl[2 * CT + 1][N2 + 1];
     __shared__ float2 tw[N2];
-    __shared__ float wmax[4];
+    __shared__ unsigned wmax[4];
     const int tid = threadIdx.x, tile = blockIdx.x;
     const long q = blockIdx.y;
     const float2* a = A + q * NC;
@@ -236,7 +238,7 @@ __global__ __launch_bounds__(256) void k_fft49_cols(const float2* __restrict__ A
     if (MODE == 1) {
         const float inv = 1.0f / (float)NC;
         float2* o = out + q * NC;
-        float m = 0.f;
+        unsigned m = 0u;
         for (int i = tid; i < ncol * N2; i += 256) {
             const int k2 = i / ncol, c = i - k2 * ncol;
             const int k1 = col_k1(c);
@@ -244,14 +246,14 @@ __global__ __launch_bounds__(256) void k_fft49_cols(const float2* __restrict__ A
             float2 z = Zl[c][k2];
             const float2 r = make_float2(z.x * inv, -z.y * inv);
             o[k1 + N1 * k2] = r;
-            m = fmaxf(m, fmaxf(fabsf(r.x), fabsf(r.y)));
+            m = max(m, max(__float_as_uint(fabsf(r.x)), __float_as_uint(fabsf(r.y))));
         }
         if (mx) {
 #pragma unroll
-            for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+            for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
             if ((tid & 63) == 0) wmax[tid >> 6] = m;
             __syncthreads();
-            if (tid == 0) atomicMax(mx, __float_as_uint(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]))));
+            if (tid == 0) atomicMax(mx, max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])));
         }
     } else {
         float2* X = out + q * XPAD;
@@ -533,7 +535,7 @@ __global__ __launch_bounds__(256) void k_spec_gather(const float2* __restrict__ 
 
 __global__ __launch_bounds__(256) void k_scale_by_max(float* __restrict__ x, const unsigned* __restrict__ mx, long n) {
     const float m = __uint_as_float(*mx);
-    if (!(m > 0.f)) return;                                            // cqtwrapper.py:209 guard
+    if (m == 0.f) return;                                              // cqtwrapper.py:209 guard; a NaN peak divides (all NaN, as there)
     float2* x2 = reinterpret_cast<float2*>(x);                          // n is even (pairs of samples)
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n / 2; i += (long)gridDim.x * 256) {
         float2 v = x2[i];

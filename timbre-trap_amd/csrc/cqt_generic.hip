@@ -214,27 +214,28 @@ __global__ __launch_bounds__(GT) void k_g_ola(const float2* __restrict__ V, cons
     }
 }
 
-// x[q][n] = 2 Re(c[n] conj(W[q][n])) / N, and the running abs-max of the whole batch (non-negative floats order like their bits)
+// x[q][n] = 2 Re(c[n] conj(W[q][n])) / N, and the running abs-max of the whole batch, taken on the bit patterns of |v|: non-negative
+// floats order like their bits and a NaN (sign cleared) lies above +inf, so a NaN sample becomes the peak, as in torch's max
 __global__ __launch_bounds__(GT) void k_g_audio(const float2* __restrict__ w, const float2* __restrict__ chirp, float* __restrict__ audio, unsigned* __restrict__ peak,
                                                 int N, int logP, long total) {                   // total = Q * N
     const float sc = 2.f / (float)N;
-    float mx = 0.f;
+    unsigned mx = 0u;
     for (long g = (long)blockIdx.x * GT + threadIdx.x; g < total; g += (long)gridDim.x * GT) {
         const long q = g / N;
         const int n = (int)(g - q * N);
         const float2 c = chirp[n], z = w[(q << logP) + n];
         const float v = (c.x * z.x + c.y * z.y) * sc;                  // Re(c conj(z))
         audio[g] = v;
-        mx = fmaxf(mx, fabsf(v));
+        mx = max(mx, __float_as_uint(fabsf(v)));
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    if ((threadIdx.x & 63) == 0 && mx > 0.f) atomicMax(peak, __float_as_uint(mx));
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o, 64));
+    if ((threadIdx.x & 63) == 0 && mx != 0u) atomicMax(peak, mx);
 }
 
 __global__ __launch_bounds__(GT) void k_g_scale(float* __restrict__ audio, const unsigned* __restrict__ peak, long total) {
     const float p = __uint_as_float(peak[0]);
-    if (!(p > 0.f)) return;                                            // cqtwrapper.py:209: only when the maximum is non-zero
+    if (p == 0.f) return;                                              // cqtwrapper.py:209: only when the maximum is non-zero (a NaN peak divides)
     for (long g = (long)blockIdx.x * GT + threadIdx.x; g < total; g += (long)gridDim.x * GT) audio[g] = audio[g] / p;
 }
 
