@@ -547,6 +547,29 @@ int tt_peak_pick(const float* x, float* out, int64_t n_outer, int F, int T, doub
 int tt_target_activations(const int* bins, const int* frames, int n, const double* weights, int radius, int F, int T,
                           double* work, double* out, void* stream);
 
+/* ---- signal-distortion ratio (csrc/sdr.hip; version 10) ------------------------------------------------------------------------------
+ * Replaces torchmetrics.audio.SignalDistortionRatio as built and called by experiments/evaluate.py:51,122-127
+ * (`sdr_module(synth, audio).item()` per track, on the device, right after sliCQ.decode): the filtered SDR of B clips of N fp32
+ * samples with L = filter_length lags, in float64, without FFTs and without a host round trip:
+ *     r[l] = sum_n t[n] t[n+l],  b[l] = sum_n t[n] p[n+l]   (linear: zeros beyond the clip's end),  0 <= l < L
+ *     Toeplitz(r / |t|^2 (+ load_diag on the diagonal)) h = b / (|t| |p|);   coh = b . h;   SDR = 10 log10(coh / (1 - coh))
+ * 1 <= L <= 512 and N >= 1, else TT_E_BADARG.  preds, target: (B, N) fp32 contiguous; every sum is taken in a fixed order (no atomics).
+ *   tt_sdr_chunk          samples per workgroup of the correlation kernel (the lengths at which its index arithmetic changes)
+ *   tt_sdr_scratch_bytes  bytes of `scratch` for tt_sdr_means and tt_sdr_correlate (experiments/evaluate.py:51,122-127)
+ *   tt_sdr_means          zero_mean=True (evaluate.py:51,122-127 leaves it False): means_out[B][2] = {mean(preds), mean(target)} per clip
+ *   tt_sdr_correlate      (experiments/evaluate.py:51,122-127) rb_out[B][2L+1] = r[0..L), b[0..L), sum p^2 of the raw signals, or of the
+ *                         signals minus `means` (tt_sdr_means' output; NULL: none), subtracted as the samples are read
+ *   tt_sdr_finish         (experiments/evaluate.py:51,122-127) norms clamped at 1e-6 like the host function, load_diag added to r[0] when
+ *                         has_load_diag != 0, Levinson recursion (L - 1 steps whatever the data); coh_out[B], sdr_out[B] float64.
+ *                         coh / (1 - coh) <= 0 gives -inf; an all-zero target gives a non-finite value, not an error. */
+int     tt_sdr_chunk(void);
+int64_t tt_sdr_scratch_bytes(int B, int64_t N, int L);
+int tt_sdr_means(const float* preds, const float* target, int B, int64_t N, void* scratch, double* means_out, void* stream);
+int tt_sdr_correlate(const float* preds, const float* target, int B, int64_t N, int L, const double* means, void* scratch,
+                     double* rb_out, void* stream);
+int tt_sdr_finish(const double* rb, int B, int L, double load_diag, int has_load_diag, double* coh_out, double* sdr_out,
+                  void* stream);
+
 /* ---- fp32-class residual blocks on the 16-bit matrix pipe ("x3": split operands), inference ----------------------------------------
  * csrc/conv_x3.hip.  The three ResidualConv2dBlocks of one wide EncoderBlock / DecoderBlock (modules.py:621-624, 690-693; C = 16, 32,
  * dilation 1..3, else TT_E_BADARG / TT_E_UNSUPPORTED) evaluated to fp32 accuracy without the fp32 matrix instructions: every fp32

@@ -25,7 +25,9 @@ SOURCES = ['cqt.hip', 'cqt_generic.hip', 'conv_generic.hip', 'conv_mfma.hip', 'c
            # the 16-bit channels-last sources a second time with fp16 elements (two-line wrappers: #define TT_F16 + #include)
            'conv_wide_f16.hip', 'conv_level_f16.hip', 'conv_stride_f16.hip', 'latent_f16.hip', 'conv_edge_f16.hip',
            # fp32-class inference blocks on split fp16 operands
-           'conv_x3.hip']
+           'conv_x3.hip',
+           # float64 signal-distortion ratio of evaluate()
+           'sdr.hip']
 
 _lib = None
 
@@ -162,6 +164,11 @@ _PROTOS = {
     'tt_segment_stats': (c_int, [P, P, I, P, P]),
     'tt_peak_pick': (c_int, [P, P, L, I, I, ctypes.c_double, I, I, P]),
     'tt_target_activations': (c_int, [P, P, I, P, I, I, I, P, P, P]),
+    'tt_sdr_chunk': (c_int, []),
+    'tt_sdr_scratch_bytes': (c_int64, [I, L, I]),
+    'tt_sdr_means': (c_int, [P, P, I, L, P, P, P]),
+    'tt_sdr_correlate': (c_int, [P, P, I, L, I, P, P, P, P]),
+    'tt_sdr_finish': (c_int, [P, I, I, ctypes.c_double, I, P, P, P]),
     'tt_l2norm': (c_int, [P, P, P, L, P]),
     'tt_adamw_step': (c_int, [P, P, P, P, P, L, F_, F_, F_, F_, F_, I, F_, I, P, P]),
     'tt_set_loss_scale': (c_float, [F_]),
