@@ -570,6 +570,36 @@ int tt_sdr_correlate(const float* preds, const float* target, int B, int64_t N, 
 int tt_sdr_finish(const double* rb, int B, int L, double load_diag, int has_load_diag, double* coh_out, double* sdr_out,
                   void* stream);
 
+/* ---- multi-pitch scoring (csrc/mpe.hip; version 11) ----------------------------------------------------------------------------------
+ * Replaces, per track, the host leg of experiments/evaluate.py:100-116 -- `to_array(transcription)`, `activations_to_multi_pitch(...,
+ * peaks_only=True)` (datasets/PitchDataset.py:309-348) and `mir_eval.multipitch.evaluate` as called from utils/experiments.py:376-378 --
+ * by per-frame integer counts computed where the activations are.  x: (F, T) fp32, T contiguous.  Nothing here uses atomics; every
+ * offset into x or into a CSR array is 64-bit.
+ *   tt_mpe_max_est / tt_mpe_max_ref   capacities of tt_mpe_match: active bins / reference pitches per frame it holds in LDS
+ *   tt_mpe_count   (evaluate.py:107-113; PitchDataset.py:309-348) n_est[t] = number of bins of frame t that pass tt_peak_pick's predicate
+ *                  of `mode` 1 (x >= threshold) or 2 (strict local maximum along F && x >= threshold), rows f >= f_valid read as zero
+ *                  first; bad_out[t] = OR of bin_bad[f] over those bins (bin_bad: F bytes, NULL: none -- the bins whose frequency lies
+ *                  outside mir_eval's [20, 5000] Hz, which mir_eval.multipitch.validate, called from experiments.py:376-378, rejects)
+ *   tt_mpe_fill    (PitchDataset.py:309-348) est_bins[est_off[t] .. est_off[t + 1]) = those bins in ascending order; est_off[T + 1] is the
+ *                  exclusive prefix sum of tt_mpe_count's n_est (formed by the caller); nothing is written at or beyond `capacity`
+ *   tt_mpe_match   (experiments.py:376-378: mir_eval.multipitch.evaluate -> resample_multipitch, compute_num_true_positives) for
+ *                  reference frame j < n_ref_frames, whose pitches are ref_midi[ref_off[j] .. ref_off[j + 1]) (float64 MIDI numbers) and
+ *                  which reads estimate frame est_idx[j] (T, or anything outside [0, T): an empty frame) with pitches
+ *                  est_midi[est_bins[..]] (est_midi: F float64):  n_est[j] = pitches in that estimate frame;  tp[j] = size of a maximum
+ *                  matching under fabs(r - e) <= window;  tp_chroma[j] = the same on fmod(., 12) values with distance
+ *                  d = fmod(|r - e|, 12), min(d, 12 - d) -- all float64, the expressions of the host scorer, so the counts are equal
+ *                  to its counts, not close to them.  A frame with more than tt_mpe_max_ref reference pitches or more than
+ *                  tt_mpe_max_est estimates gets tp[j] = -1 and nothing else written. */
+int tt_mpe_max_est(void);
+int tt_mpe_max_ref(void);
+int tt_mpe_count(const float* x, int F, int T, double threshold, int mode, int f_valid, const unsigned char* bin_bad, int* n_est,
+                 int* bad_out, void* stream);
+int tt_mpe_fill(const float* x, int F, int T, double threshold, int mode, int f_valid, const int64_t* est_off, int64_t capacity,
+                int* est_bins, void* stream);
+int tt_mpe_match(const int* est_idx, int n_ref_frames, int T, const int64_t* est_off, const int* est_bins, const double* est_midi,
+                 int F, const int64_t* ref_off, const double* ref_midi, double window, int* tp, int* tp_chroma, int* n_est,
+                 void* stream);
+
 /* ---- fp32-class residual blocks on the 16-bit matrix pipe ("x3": split operands), inference ----------------------------------------
  * csrc/conv_x3.hip.  The three ResidualConv2dBlocks of one wide EncoderBlock / DecoderBlock (modules.py:621-624, 690-693; C = 16, 32,
  * dilation 1..3, else TT_E_BADARG / TT_E_UNSUPPORTED) evaluated to fp32 accuracy without the fp32 matrix instructions: every fp32

@@ -27,7 +27,9 @@ SOURCES = ['cqt.hip', 'cqt_generic.hip', 'conv_generic.hip', 'conv_mfma.hip', 'c
            # fp32-class inference blocks on split fp16 operands
            'conv_x3.hip',
            # float64 signal-distortion ratio of evaluate()
-           'sdr.hip']
+           'sdr.hip',
+           # multi-pitch scores of evaluate(): compaction of the activation map and per-frame maximum matching
+           'mpe.hip']
 
 _lib = None
 
@@ -169,6 +171,11 @@ _PROTOS = {
     'tt_sdr_means': (c_int, [P, P, I, L, P, P, P]),
     'tt_sdr_correlate': (c_int, [P, P, I, L, I, P, P, P, P]),
     'tt_sdr_finish': (c_int, [P, I, I, ctypes.c_double, I, P, P, P]),
+    'tt_mpe_max_est': (c_int, []),
+    'tt_mpe_max_ref': (c_int, []),
+    'tt_mpe_count': (c_int, [P, I, I, ctypes.c_double, I, I, P, P, P, P]),
+    'tt_mpe_fill': (c_int, [P, I, I, ctypes.c_double, I, I, P, L, P, P]),
+    'tt_mpe_match': (c_int, [P, I, I, P, P, P, I, P, P, ctypes.c_double, P, P, P, P]),
     'tt_l2norm': (c_int, [P, P, P, L, P]),
     'tt_adamw_step': (c_int, [P, P, P, P, P, L, F_, F_, F_, F_, F_, I, F_, I, P, P]),
     'tt_set_loss_scale': (c_float, [F_]),

@@ -16,8 +16,8 @@ from .experiments import (CosineWarmup, seed_everything, gradient_statistics, su
 from .processing import to_array, debug_nans, filter_non_peaks, threshold, peaks_above
 from .targets import multi_pitch_to_activations, activations_to_multi_pitch, hz_to_midi, midi_to_hz
 from .slicing import slice_audio, slice_times, resample_multi_pitch, nearest_indices, ExcerptSlicer
-from .metrics import (MultipitchEvaluator, multipitch_metrics, signal_distortion_ratio, signal_distortion_ratio_device,
-                      SignalDistortionRatio)
+from .metrics import (MultipitchEvaluator, multipitch_metrics, multipitch_metrics_device, multipitch_counts_device,
+                      signal_distortion_ratio, signal_distortion_ratio_device, SignalDistortionRatio)
 from .trainloop import (make_schedulers, checkpoints_for, StepLogger, TrainingState, save_checkpoint, print_and_log,
                         log_gradient_norms, TRAIN_TAGS)
 

@@ -12,6 +12,10 @@ implemented by torchmetrics / fast_bss_eval).  PARITY UNPINNED against the packa
 is no network); pinned instead by known-answer tests (tests/test_metrics.py) and, for the SDR, by an independent dense
 least-squares derivation of the same quantity.  Host code in float64, as in the reference (NumPy lists / CPU tensors).
 
+``multipitch_counts_device`` / ``multipitch_metrics_device`` / ``MultipitchEvaluator.evaluate_activations`` give the scores of
+``multipitch_metrics`` bit for bit from activations that stay on the device (csrc/mpe.hip: compaction of the activation map to
+per-frame bin lists, a maximum matching per reference frame in float64, integer sums; one small copy back per track).
+
 ``signal_distortion_ratio_device`` / ``SignalDistortionRatio`` compute the same SDR where ``experiments/evaluate.py:51,122-127``
 asks for it -- on the device, right after ``sliCQ.decode`` -- in float64 HIP kernels (csrc/sdr.hip: direct correlation sums and a
 Levinson recursion instead of FFTs and a dense solve); ``signal_distortion_ratio`` stays the float64 yardstick they are tested against.
@@ -24,11 +28,22 @@ import numpy as np
 import torch
 
 from .. import _hip
+from .targets import midi_to_hz
 
 __all__ = ['resample_multipitch', 'frequencies_to_midi', 'match_count', 'multipitch_metrics', 'MultipitchEvaluator',
+           'multipitch_counts_device', 'multipitch_metrics_device', 'mpe_compact', 'MPE_MAX_EST', 'MPE_MAX_REF',
            'signal_distortion_ratio', 'signal_distortion_ratio_device', 'SignalDistortionRatio', 'SDR_CHUNK', 'SDR_MAX_FILTER']
 
 MAX_FREQ, MIN_FREQ = 5000.0, 20.0            # mir_eval.multipitch validation limits (evaluate.py:44-48 masks bins above 5 kHz)
+
+
+def _nearest_frame_index(times, target_times, n):
+    """Index of the frame of ``times`` (n of them, float64, non-empty) nearest to every target time; ties go to the earlier frame;
+    ``n`` for targets outside [times[0], times[-1]] (an empty frame)."""
+    half = times / 2.0
+    mids = half[1:] + half[:-1]
+    idx = np.clip(np.searchsorted(mids, target_times, side='left'), 0, n - 1)
+    return np.where((target_times < times[0]) | (target_times > times[-1]), n, idx)
 
 
 def resample_multipitch(times, frequencies, target_times):
@@ -42,11 +57,7 @@ def resample_multipitch(times, frequencies, target_times):
     times = np.asarray(times, dtype=np.float64)
     if times.size == 0:
         return [np.array([])] * len(target_times)
-    n = len(frequencies)
-    half = times / 2.0
-    mids = half[1:] + half[:-1]
-    idx = np.clip(np.searchsorted(mids, target_times, side='left'), 0, n - 1)
-    idx = np.where((target_times < times[0]) | (target_times > times[-1]), n, idx)
+    idx = _nearest_frame_index(times, target_times, len(frequencies))
     vals = list(frequencies) + [np.array([])]
     return [vals[int(i)] for i in idx]
 
@@ -97,24 +108,31 @@ def match_count(ref_midi, est_midi, window=0.5, chroma=False):
     return np.array([_max_matching(r, e, window, chroma) for r, e in zip(ref_midi, est_midi)], dtype=np.float64)
 
 
-def _prf_accuracy(tp, n_ref, n_est):
-    tps, nr, ne = tp.sum(), n_ref.sum(), n_est.sum()
+def _prf_from_sums(tps, nr, ne, denom):
+    """Precision, recall, accuracy from sum(tp), sum(n_ref), sum(n_est), sum(n_est + n_ref - tp) as float64."""
     precision = tps / ne if ne > 0 else 0.0
     recall = tps / nr if nr > 0 else 0.0
-    denom = (n_est + n_ref - tp).sum()
     accuracy = tps / denom if denom > 0 else 0.0
     return float(precision), float(recall), float(accuracy)
 
 
-def _error_scores(tp, n_ref, n_est):
-    nr = n_ref.sum()
+def _errors_from_sums(nr, sub, miss, fa, tot):
+    """The four error scores from sum(n_ref) and the sums of their per-frame numerators, as float64."""
     if nr == 0:
         return 0.0, 0.0, 0.0, 0.0
-    e_sub = (np.minimum(n_ref, n_est) - tp).sum() / nr
-    e_miss = np.maximum(n_ref - n_est, 0).sum() / nr
-    e_fa = np.maximum(n_est - n_ref, 0).sum() / nr
-    e_tot = (np.maximum(n_ref, n_est) - tp).sum() / nr
-    return float(e_sub), float(e_miss), float(e_fa), float(e_tot)
+    return float(sub / nr), float(miss / nr), float(fa / nr), float(tot / nr)
+
+
+def _prf_accuracy(tp, n_ref, n_est):
+    return _prf_from_sums(tp.sum(), n_ref.sum(), n_est.sum(), (n_est + n_ref - tp).sum())
+
+
+def _error_scores(tp, n_ref, n_est):
+    return _errors_from_sums(n_ref.sum(), (np.minimum(n_ref, n_est) - tp).sum(), np.maximum(n_ref - n_est, 0).sum(),
+                             np.maximum(n_est - n_ref, 0).sum(), (np.maximum(n_ref, n_est) - tp).sum())
+
+
+_SCORE_KEYS = ['Precision', 'Recall', 'Accuracy', 'Substitution Error', 'Miss Error', 'False Alarm Error', 'Total Error']
 
 
 def multipitch_metrics(ref_time, ref_freqs, est_time, est_freqs, window=0.5):
@@ -132,7 +150,7 @@ def multipitch_metrics(ref_time, ref_freqs, est_time, est_freqs, window=0.5):
             f = np.asarray(f)
             if f.size and (f.max() > MAX_FREQ or f.min() < MIN_FREQ):
                 raise ValueError('%s frequencies must lie in [%g, %g] Hz' % (name, MIN_FREQ, MAX_FREQ))
-    keys = ['Precision', 'Recall', 'Accuracy', 'Substitution Error', 'Miss Error', 'False Alarm Error', 'Total Error']
+    keys = _SCORE_KEYS
     out = {k: 0.0 for k in keys + ['Chroma ' + k for k in keys]}
     if len(ref_time) == 0 or len(est_time) == 0:
         return out
@@ -180,12 +198,200 @@ class MultipitchEvaluator(object):
             std_dev[key] = round(np.std(std_dev[key]), 5)
         return mean, std_dev
 
-    def evaluate(self, times_est, multi_pitch_est, times_ref, multi_pitch_ref):
-        scores = multipitch_metrics(times_ref, multi_pitch_ref, times_est, multi_pitch_est, window=self.tolerance)
+    @staticmethod
+    def _tagged(scores):
         results = {k.lower(): v for k, v in scores.items()}
         pr, rc = results['precision'], results['recall']
         results['f1-score'] = 2 * pr * rc / (pr + rc + sys.float_info.epsilon)
         return {'mpe/' + k: v for k, v in results.items()}
+
+    def evaluate(self, times_est, multi_pitch_est, times_ref, multi_pitch_ref):
+        return self._tagged(multipitch_metrics(times_ref, multi_pitch_ref, times_est, multi_pitch_est, window=self.tolerance))
+
+    def evaluate_activations(self, times_est, activations, midi_freqs, times_ref, multi_pitch_ref, n_valid_bins=0):
+        """
+        ``evaluate`` for activations that are still on the device -- the (F, T) or (1, F, T) tensor ``model.to_activations``
+        returned -- instead of frame lists: the same ``mpe/...`` dictionary as ``evaluate(times_est,
+        activations_to_multi_pitch(masked activations, midi_freqs, peaks_only=True), times_ref, multi_pitch_ref)``, bit for bit,
+        without downloading the map (reference ``experiments/evaluate.py:100-116``).  ``n_valid_bins`` > 0 zeroes the rows from
+        that bin upwards first (``evaluate.py:107-112``).
+        """
+        return self._tagged(multipitch_metrics_device(times_ref, multi_pitch_ref, times_est, activations, midi_freqs,
+                                                      window=self.tolerance, n_valid_bins=n_valid_bins))
+
+
+# ---- multi-pitch scores on the device (csrc/mpe.hip) -------------------------------------------------------------------------
+
+MPE_MAX_EST = 256         # active bins per frame the matching kernel holds (= tt_mpe_max_est(), checked on first use)
+MPE_MAX_REF = 64          # reference pitches per frame it holds (= tt_mpe_max_ref())
+# the integer sums the fourteen scores are formed from, in the order of the one int64 tensor that comes back per track
+_MPE_SUMS = ('tp', 'tp_chroma', 'n_ref', 'n_est', 'min', 'max', 'miss', 'false_alarm')
+
+
+def _mpe_sums(tp, tpc, n_ref, n_est, xp):
+    """The eight sums of _MPE_SUMS over int64 per-frame counts (``xp``: torch for device tensors, np for arrays)."""
+    zero = n_ref * 0
+    return [tp.sum(), tpc.sum(), n_ref.sum(), n_est.sum(), xp.minimum(n_ref, n_est).sum(), xp.maximum(n_ref, n_est).sum(),
+            xp.maximum(n_ref - n_est, zero).sum(), xp.maximum(n_est - n_ref, zero).sum()]
+
+
+def _scores_from_sums(sums):
+    """``multipitch_metrics``' dictionary from the integer sums (exact in float64: every sum is far below 2^53)."""
+    s = {k: np.float64(v) for k, v in zip(_MPE_SUMS, sums)}
+    out = {}
+    for prefix, tps in (('', s['tp']), ('Chroma ', s['tp_chroma'])):
+        prf = _prf_from_sums(tps, s['n_ref'], s['n_est'], s['n_est'] + s['n_ref'] - tps)
+        err = _errors_from_sums(s['n_ref'], s['min'] - tps, s['miss'], s['false_alarm'], s['max'] - tps)
+        for k, v in zip(_SCORE_KEYS, prf + err):
+            out[prefix + k] = v
+    return out
+
+
+def _mpe_reference_csr(ref_freqs):
+    """Ragged per-frame reference pitches (Hz) -> (offsets int64 [K + 1], flat float64 Hz), range-checked like multipitch_metrics."""
+    frames = [np.asarray(f, dtype=np.float64).ravel() for f in ref_freqs]
+    off = np.zeros(len(frames) + 1, dtype=np.int64)
+    np.cumsum(np.array([f.size for f in frames], dtype=np.int64), out=off[1:])
+    flat = np.concatenate(frames) if off[-1] else np.empty(0)
+    if flat.size and (flat.max() > MAX_FREQ or flat.min() < MIN_FREQ):
+        raise ValueError('reference frequencies must lie in [%g, %g] Hz' % (MIN_FREQ, MAX_FREQ))
+    return off, flat
+
+
+def _mpe_bin_tables(midi_freqs):
+    """Per bin: the MIDI number the host route compares (bin -> Hz by ``activations_to_multi_pitch`` -> MIDI by
+    ``frequencies_to_midi``: not bit-identical to ``midi_freqs``) and whether its frequency fails mir_eval's range check."""
+    hz = midi_to_hz(np.asarray(midi_freqs, dtype=np.float64))
+    return frequencies_to_midi([hz])[0], ((hz > MAX_FREQ) | (hz < MIN_FREQ)).astype(np.uint8)
+
+
+def _mpe_activations(activations):
+    if not isinstance(activations, torch.Tensor):
+        raise RuntimeError('multipitch scoring on the device takes a GPU tensor of activations (got %s); the host function '
+                           'multipitch_metrics takes frame lists' % type(activations).__name__)
+    _hip.require_cuda(activations)
+    x = activations.detach()
+    if x.dim() == 3 and x.size(0) == 1:
+        x = x[0]
+    if x.dim() != 2:
+        raise ValueError('activations must be (F, T) or (1, F, T) (got %s)' % (tuple(activations.shape),))
+    if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError('unsupported dtype %s' % x.dtype)
+    return x.to(torch.float32).contiguous()
+
+
+def mpe_compact(activations, t=0.5, peaks_only=True, n_valid_bins=0, bin_bad=None):
+    """
+    The activation map as per-frame lists of active bins, on the device: ``(est_off int64 [T + 1], est_bins int32, n_est int32
+    [T], bad int32 [T])`` with frame ``f``'s bins, ascending, at ``est_bins[est_off[f]:est_off[f + 1]]`` -- the non-zeros of
+    ``peaks_above(x, t, n_valid_bins)`` (``peaks_only``) or of ``threshold`` of the masked map.  ``est_bins`` is allocated for the
+    most bins the predicate can let through, so no count has to come back to the host in between.
+    """
+    x = _mpe_activations(activations)
+    F, T = x.shape
+    if F < 1 or T < 1:
+        raise ValueError('activations hold no bin or no frame')
+    lib, dev = _hip.lib(), x.device
+    mode = 2 if peaks_only else 1
+    fv = n_valid_bins if 0 < n_valid_bins < F else F
+    per_frame = (fv + 1) // 2 if peaks_only else (fv if t > 0 else F)      # strict peaks cannot be adjacent
+    n_est = torch.empty(T, dtype=torch.int32, device=dev)
+    bad = torch.empty(T, dtype=torch.int32, device=dev)
+    est_bins = torch.empty(max(per_frame * T, 1), dtype=torch.int32, device=dev)
+    bad_t = None if bin_bad is None else torch.from_numpy(np.ascontiguousarray(bin_bad, dtype=np.uint8)).to(dev)
+    with torch.cuda.device(dev):
+        st = _hip.stream_ptr()
+        _hip.check(lib.tt_mpe_count(_hip.ptr(x), F, T, float(t), mode, int(n_valid_bins), _hip.ptr(bad_t), _hip.ptr(n_est), _hip.ptr(bad), st),
+                   'tt_mpe_count')
+        est_off = torch.zeros(T + 1, dtype=torch.int64, device=dev)
+        est_off[1:] = torch.cumsum(n_est, 0, dtype=torch.int64)
+        _hip.check(lib.tt_mpe_fill(_hip.ptr(x), F, T, float(t), mode, int(n_valid_bins), _hip.ptr(est_off), est_bins.numel(),
+                                   _hip.ptr(est_bins), st), 'tt_mpe_fill')
+    return est_off, est_bins, n_est, bad
+
+
+def multipitch_counts_device(ref_time, ref_freqs, est_time, activations, midi_freqs, window=0.5, t=0.5, peaks_only=True, n_valid_bins=0):
+    """
+    What ``multipitch_metrics(ref_time, ref_freqs, est_time, activations_to_multi_pitch(activations, midi_freqs, peaks_only, t))``
+    counts per reference frame, from ``activations`` -- a CUDA fp32 / fp16 / bf16 tensor (F, T) or (1, F, T), 16-bit upcast to fp32
+    -- that never leave the device: a dict of int32 device tensors ``tp``, ``tp_chroma``, ``n_ref``, ``n_est`` (one entry per
+    reference frame), ``n_host_frames`` and ``sums`` (the eight integer sums the scores are formed from, int64 ndarray).
+
+    On the host, vectorised over the ragged reference only: the reference as CSR in MIDI numbers, the estimate frame every
+    reference frame reads (``resample_multipitch``'s arithmetic), the per-bin MIDI table of the host route.  On the device:
+    tt_mpe_count -> prefix sum -> tt_mpe_fill -> tt_mpe_match -> integer sums, then ONE copy of ten int64 values.  A frame
+    with more than MPE_MAX_REF reference pitches or more than MPE_MAX_EST active bins comes back flagged; only those frames'
+    bins are downloaded and matched by ``_max_matching`` (``n_host_frames`` of them; none at evaluate()'s settings, where a frame
+    holds at most 236 peaks).  ``ValueError`` as from the host function: length mismatch, reference or -- known after the copy --
+    estimated frequency outside [20, 5000] Hz.  CPU tensors raise ``RuntimeError``: there is no CPU fallback.
+    """
+    x = _mpe_activations(activations)
+    F, T = x.shape
+    dev = x.device
+    ref_time = np.asarray(ref_time, dtype=np.float64)
+    est_time = np.asarray(est_time, dtype=np.float64)
+    midi_freqs = np.asarray(midi_freqs, dtype=np.float64)
+    if len(ref_time) != len(ref_freqs) or len(est_time) != T:
+        raise ValueError('time and frequency lists must have the same number of frames')
+    if midi_freqs.shape != (F,):
+        raise ValueError('midi_freqs must hold one value per bin (%d), got shape %s' % (F, midi_freqs.shape))
+    ref_off, ref_hz = _mpe_reference_csr(ref_freqs)
+    K = len(ref_time)
+    if K == 0 or T == 0 or F == 0:
+        empty = torch.zeros(K, dtype=torch.int32, device=dev)
+        return dict(tp=empty, tp_chroma=empty.clone(), n_ref=empty.clone(), n_est=empty.clone(), n_host_frames=0,
+                    sums=np.zeros(len(_MPE_SUMS), dtype=np.int64))
+    lib = _hip.lib()
+    if (lib.tt_mpe_max_est(), lib.tt_mpe_max_ref()) != (MPE_MAX_EST, MPE_MAX_REF):
+        raise RuntimeError('libttrap_hip.so was built with capacities (%d, %d), metrics says (%d, %d)'
+                           % (lib.tt_mpe_max_est(), lib.tt_mpe_max_ref(), MPE_MAX_EST, MPE_MAX_REF))
+    ref_midi = frequencies_to_midi([ref_hz])[0]
+    est_idx = _nearest_frame_index(est_time, ref_time, T).astype(np.int32)
+    est_midi, bin_bad = _mpe_bin_tables(midi_freqs)
+
+    est_off, est_bins, n_act, bad = mpe_compact(x, t, peaks_only, n_valid_bins, bin_bad)
+    ref_off_d = torch.from_numpy(ref_off).to(dev)
+    ref_midi_d = torch.from_numpy(ref_midi if ref_midi.size else np.zeros(1)).to(dev)
+    est_idx_d = torch.from_numpy(est_idx).to(dev)
+    est_midi_d = torch.from_numpy(est_midi).to(dev)
+    tp = torch.empty(K, dtype=torch.int32, device=dev)
+    tpc = torch.zeros(K, dtype=torch.int32, device=dev)
+    n_est = torch.zeros(K, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.tt_mpe_match(_hip.ptr(est_idx_d), K, T, _hip.ptr(est_off), _hip.ptr(est_bins), _hip.ptr(est_midi_d), F,
+                                    _hip.ptr(ref_off_d), _hip.ptr(ref_midi_d), float(window), _hip.ptr(tp), _hip.ptr(tpc), _hip.ptr(n_est),
+                                    _hip.stream_ptr()), 'tt_mpe_match')
+    n_ref = (ref_off_d[1:] - ref_off_d[:-1]).to(torch.int32)
+    flagged = tp < 0
+    done = (~flagged).to(torch.int64)                  # flagged frames stay out of the device sums: the host adds theirs
+    sums = _mpe_sums(tp * done, tpc * done, n_ref * done, n_est * done, torch)
+    back = torch.stack(sums + [flagged.sum(), bad.sum(dtype=torch.int64)]).cpu().numpy()        # the one device -> host copy
+    if back[-1]:
+        raise ValueError('estimate frequencies must lie in [%g, %g] Hz' % (MIN_FREQ, MAX_FREQ))
+    sums, n_host = back[:len(_MPE_SUMS)].copy(), int(back[-2])
+    if n_host:
+        # over a capacity of the kernel: these frames alone are matched by the host function, from their own bins
+        js = torch.nonzero(flagged).flatten()
+        fr = est_idx_d[js].to(torch.int64).clamp(max=T - 1)
+        spans = torch.stack([js, est_off[fr], est_off[fr + 1]], 1).cpu().numpy()
+        got = np.zeros((n_host, 4), dtype=np.int64)
+        for row, (j, lo, hi) in zip(got, spans):
+            bins = est_bins[lo:hi].cpu().numpy() if est_idx[j] < T else np.empty(0, dtype=np.int64)
+            r, e = ref_midi[ref_off[j]:ref_off[j + 1]], est_midi[bins]
+            row[:] = (_max_matching(r, e, window, False), _max_matching(np.mod(r, 12), np.mod(e, 12), window, True), len(r), len(e))
+        sums += np.array(_mpe_sums(got[:, 0], got[:, 1], got[:, 2], got[:, 3], np), dtype=np.int64)
+        fix = torch.from_numpy(got.astype(np.int32)).to(dev)
+        tp[js], tpc[js], n_est[js] = fix[:, 0], fix[:, 1], fix[:, 3]
+    return dict(tp=tp, tp_chroma=tpc, n_ref=n_ref, n_est=n_est, n_host_frames=n_host, sums=sums)
+
+
+def multipitch_metrics_device(ref_time, ref_freqs, est_time, activations, midi_freqs, window=0.5, t=0.5, peaks_only=True, n_valid_bins=0):
+    """
+    The fourteen scores of ``multipitch_metrics`` (same keys, same float64 values bit for bit) for estimates given as device
+    activations: see ``multipitch_counts_device``.  Empty ``ref_time`` or ``est_time`` give the all-zero dictionary.
+    """
+    counts = multipitch_counts_device(ref_time, ref_freqs, est_time, activations, midi_freqs, window, t, peaks_only, n_valid_bins)
+    return _scores_from_sums(counts['sums'])
 
 
 # ---- SDR --------------------------------------------------------------------------------------------------------------

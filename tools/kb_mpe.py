@@ -1,0 +1,123 @@
+"""
+The device multi-pitch scorer (csrc/mpe.hip) against the host route on one machine, on a synthetic five-minute track at evaluate()'s
+geometry: 540 bins (472 below 5 kHz), 102 400 frames at 341 frames / s, 3-6 peaks at or above 0.5 per frame like a trained model's
+output, references on a 10 ms grid with 0-6 pitches each (most of them within a fraction of a semitone of an estimate).
+
+    python tools/kb_mpe.py [--iters 5] [--host-iters 1] [--frames 102400]
+
+One JSON line:
+  download_ms        to_array(activations): the (F, T) fp32 map to the host (evaluate.py:101)
+  to_multi_pitch_ms  rows >= 472 zeroed, then activations_to_multi_pitch(ndarray, midi_freqs, peaks_only=True) (evaluate.py:105-113)
+  metrics_ms         multipitch_metrics on the frame lists (evaluate.py:116)
+  host_ms            their sum: what evaluate() pays per track on the host route
+  device_ms          multipitch_metrics_device on the device tensor, warm, host clock between two device synchronisations (its one
+                     copy back included), median over --iters
+  compact_ms         mpe_compact alone (tt_mpe_count, prefix sum, tt_mpe_fill) between two HIP events
+  equal              the fourteen scores of the two routes compare equal (==)
+"""
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, 'timbre-trap_amd'))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+F, FV = 540, 472
+
+
+def synthetic_track(n_frames, dev):
+    g = torch.Generator(device=dev).manual_seed(n_frames)
+    x = 0.45 * torch.rand(F, n_frames, generator=g, device=dev)
+    high = torch.rand(F, n_frames, generator=g, device=dev) < 4.5 / FV
+    return torch.where(high, 0.5 + 0.5 * torch.rand(F, n_frames, generator=g, device=dev), x)
+
+
+def references(frames, est_time, rng):
+    """A 10 ms grid over the track; per frame 0-6 pitches: estimates of the nearest frame moved by N(0, 0.3) semitones, or anywhere."""
+    ref_time = np.arange(0.0, est_time[-1], 0.01)
+    nearest = np.clip(np.rint((ref_time - est_time[0]) * 341.0).astype(np.int64), 0, len(frames) - 1)
+    ref_freqs = []
+    for i in nearest:
+        n = int(rng.integers(0, 7))
+        est = frames[i]
+        near = est[rng.integers(0, len(est), size=n)] if len(est) else np.empty(0)
+        anywhere = 27.5 * 2.0 ** rng.uniform(0.0, 7.0, size=n - len(near))
+        f = np.concatenate([near * 2.0 ** (rng.normal(0.0, 0.3, size=len(near)) / 12.0), anywhere])
+        ref_freqs.append(np.clip(f, 20.0, 5000.0))
+    return ref_time, ref_freqs
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--iters', type=int, default=5)
+    ap.add_argument('--host-iters', type=int, default=1)
+    ap.add_argument('--frames', type=int, default=102400)
+    args = ap.parse_args()
+    from timbre_trap.utils import activations_to_multi_pitch, multipitch_metrics, multipitch_metrics_device, to_array
+    from timbre_trap.utils.metrics import mpe_compact, multipitch_counts_device
+    dev = torch.device('cuda:0')
+    midi_freqs = 16.76557586 + np.arange(F) / 5.0
+    x = synthetic_track(args.frames, dev)
+    est_time = np.arange(args.frames) / 341.0
+
+    def host_lists():
+        t0 = time.perf_counter()
+        a = to_array(x)
+        t1 = time.perf_counter()
+        a[FV:] = 0
+        frames = activations_to_multi_pitch(a, midi_freqs, peaks_only=True)
+        return frames, (t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3
+
+    frames, _, _ = host_lists()                                # once untimed; its lists also seed the references
+    ref_time, ref_freqs = references(frames, est_time, np.random.default_rng(0))
+    per_frame = np.array([len(f) for f in frames])
+
+    def device():
+        return multipitch_metrics_device(ref_time, ref_freqs, est_time, x, midi_freqs, n_valid_bins=FV)
+
+    dev_scores = device()                                      # once untimed: lazy kernel loading, allocator growth
+    counts = multipitch_counts_device(ref_time, ref_freqs, est_time, x, midi_freqs, n_valid_bins=FV)
+    dev_ms, compact_ms = [], []
+    for _ in range(args.iters):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        device()
+        torch.cuda.synchronize()
+        dev_ms.append((time.perf_counter() - t0) * 1e3)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        mpe_compact(x, 0.5, True, FV)
+        b.record()
+        b.synchronize()
+        compact_ms.append(a.elapsed_time(b))
+    down, lists, metr, host_scores = [], [], [], None          # --host-iters 0: device figures only (profiler runs)
+    for _ in range(args.host_iters):
+        frames, d_ms, l_ms = host_lists()
+        t0 = time.perf_counter()
+        host_scores = multipitch_metrics(ref_time, ref_freqs, est_time, frames)
+        metr.append((time.perf_counter() - t0) * 1e3)
+        down.append(d_ms)
+        lists.append(l_ms)
+    med = statistics.median
+    host_ms = med(down) + med(lists) + med(metr) if down else None
+    print(json.dumps(dict(frames=args.frames, seconds=round(args.frames / 341.0, 1), ref_frames=len(ref_time),
+                          peaks_per_frame_mean=round(float(per_frame.mean()), 2), peaks_per_frame_max=int(per_frame.max()),
+                          ref_pitches=int(sum(len(f) for f in ref_freqs)), n_host_frames=counts['n_host_frames'],
+                          f1=round(2 * dev_scores['Precision'] * dev_scores['Recall'] / (dev_scores['Precision'] + dev_scores['Recall'] + 1e-16), 6),
+                          device_ms=round(med(dev_ms), 3), device_ms_min=round(min(dev_ms), 3), device_ms_max=round(max(dev_ms), 3),
+                          compact_ms=round(med(compact_ms), 3),
+                          download_ms=round(med(down), 1) if down else None, to_multi_pitch_ms=round(med(lists), 1) if down else None,
+                          metrics_ms=round(med(metr), 1) if down else None, host_ms=round(host_ms, 1) if down else None,
+                          host_over_device=round(host_ms / med(dev_ms), 1) if down else None,
+                          equal=(host_scores == dev_scores) if down else None)), flush=True)
+
+
+if __name__ == '__main__':
+    main()
