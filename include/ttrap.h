@@ -600,6 +600,38 @@ int tt_mpe_match(const int* est_idx, int n_ref_frames, int T, const int64_t* est
                  int F, const int64_t* ref_off, const double* ref_midi, double window, int* tp, int* tp_chroma, int* n_est,
                  void* stream);
 
+/* ---- track audio: mono mix, sample-rate conversion, inf-norm (csrc/resample.hip; version 12) ----------------------------------------
+ * Replaces the three lines of AudioDataset.get_audio (timbre_trap/datasets/AudioDataset.py:69-77) that stand between a decoded file
+ * and the CQT -- `torch.mean(audio, dim=0, keepdim=True)`, `torchaudio.functional.resample(audio, fs, self.sample_rate)`,
+ * `audio /= audio.abs().max()` when that maximum is non-zero -- for B tracks x of C channels and L samples, (B, C, L) fp32:
+ *     y[b][q new + p] = sum_{k < K} h[p][k] xz[b][q orig + k - width],   K = 2 width + orig,   0 <= p < new,
+ * xz = the mono mix (channels added in index order in fp32, then one IEEE divide by C) read as zero outside [0, L); the first
+ * Lout = ceil(new L / orig) outputs are kept: conv1d(pad(x, (width, width + orig)), h, stride = orig) transposed and flattened, the
+ * arithmetic of torchaudio's sinc resampler.  orig, new: the two rates divided by their gcd.  Every output is one chain of K fused
+ * multiply-adds in ascending k; nothing here uses atomics, results are bit-reproducible.
+ *   tt_resample_tile         (AudioDataset.py:73) frames q per workgroup of the general kernel: the lengths tile orig at which its
+ *                            index arithmetic changes
+ *   tt_resample_direct_tile  (AudioDataset.py:73) the same for the kernel that serves new <= 4 with orig <= 8 (2:1, 1:2, 3:2), which
+ *                            has one thread per output and does not pay for the general kernel's phase walk
+ *   tt_resample_max_taps / tt_resample_max_phases   (AudioDataset.py:73) capacities: K <= max_taps, new <= max_phases; beyond them
+ *                            tt_resample and tt_resample_partials return TT_E_BADARG
+ *   tt_resample_partials     (AudioDataset.py:76-77) peak slots per clip that tt_resample fills for a track of L samples (= its workgroups
+ *                            per clip), or TT_E_BADARG
+ *   tt_resample              (AudioDataset.py:70-73) taps_t: the tap table TRANSPOSED, fp32 [K][new] (a wavefront runs along the
+ *                            phases and reads a row coalesced); y: (B, Lout), Lout as above or TT_E_BADARG.  peak_partials non-NULL:
+ *                            (B, tt_resample_partials(L, orig, new)) floats, every workgroup stores the maximum of |y| over the
+ *                            outputs it wrote into a slot of its own; a NaN output makes the slot NaN (torch's max, not fmaxf)
+ *   tt_resample_normalize    (AudioDataset.py:75-77) per clip: peak = maximum of its n_partials_per_clip slots (NaN wins);
+ *                            y /= peak with an IEEE divide unless peak == 0 (a NaN peak is non-zero, as in Python's `if tensor:`) */
+int     tt_resample_tile(void);
+int     tt_resample_direct_tile(void);
+int     tt_resample_max_taps(void);
+int     tt_resample_max_phases(void);
+int64_t tt_resample_partials(int64_t L, int orig, int nnew);
+int tt_resample(const float* x, int B, int C, int64_t L, const float* taps_t, int orig, int nnew, int width, float* y, int64_t Lout,
+                float* peak_partials, void* stream);
+int tt_resample_normalize(float* y, int B, int64_t Lout, const float* peak_partials, int64_t n_partials_per_clip, void* stream);
+
 /* ---- fp32-class residual blocks on the 16-bit matrix pipe ("x3": split operands), inference ----------------------------------------
  * csrc/conv_x3.hip.  The three ResidualConv2dBlocks of one wide EncoderBlock / DecoderBlock (modules.py:621-624, 690-693; C = 16, 32,
  * dilation 1..3, else TT_E_BADARG / TT_E_UNSUPPORTED) evaluated to fp32 accuracy without the fp32 matrix instructions: every fp32

@@ -29,7 +29,9 @@ SOURCES = ['cqt.hip', 'cqt_generic.hip', 'conv_generic.hip', 'conv_mfma.hip', 'c
            # float64 signal-distortion ratio of evaluate()
            'sdr.hip',
            # multi-pitch scores of evaluate(): compaction of the activation map and per-frame maximum matching
-           'mpe.hip']
+           'mpe.hip',
+           # mono mix, sample-rate conversion and inf-norm of whole tracks (AudioDataset.get_audio)
+           'resample.hip']
 
 _lib = None
 
@@ -176,6 +178,13 @@ _PROTOS = {
     'tt_mpe_count': (c_int, [P, I, I, ctypes.c_double, I, I, P, P, P, P]),
     'tt_mpe_fill': (c_int, [P, I, I, ctypes.c_double, I, I, P, L, P, P]),
     'tt_mpe_match': (c_int, [P, I, I, P, P, P, I, P, P, ctypes.c_double, P, P, P, P]),
+    'tt_resample_tile': (c_int, []),
+    'tt_resample_direct_tile': (c_int, []),
+    'tt_resample_max_taps': (c_int, []),
+    'tt_resample_max_phases': (c_int, []),
+    'tt_resample_partials': (c_int64, [L, I, I]),
+    'tt_resample': (c_int, [P, I, I, L, P, I, I, I, P, L, P, P]),
+    'tt_resample_normalize': (c_int, [P, I, L, P, L, P]),
     'tt_l2norm': (c_int, [P, P, P, L, P]),
     'tt_adamw_step': (c_int, [P, P, P, P, P, L, F_, F_, F_, F_, F_, I, F_, I, P, P]),
     'tt_set_loss_scale': (c_float, [F_]),

@@ -10,6 +10,7 @@ from pkgutil import extend_path
 
 __path__ = extend_path(__path__, __name__)
 
+from ..utils.audio import prepare_audio
 from ..utils.slicing import ExcerptSlicer
 from ..utils.targets import activations_to_multi_pitch, multi_pitch_to_activations
 
@@ -37,4 +38,9 @@ except Exception as _e:                          # no reference on the path, or 
         activations_to_multi_pitch = staticmethod(activations_to_multi_pitch)
 
     class AudioDataset(ExcerptSlicer):
-        """Stand-in with the reference's ``slice_audio`` arithmetic."""
+        """
+        Stand-in with the reference's ``slice_audio`` arithmetic and, as the static ``prepare_audio(waveform, fs, sample_rate)``,
+        the mono mix, sample-rate conversion and inf-norm of ``get_audio`` (``AudioDataset.py:70-77``) on the device.
+        """
+
+        prepare_audio = staticmethod(prepare_audio)

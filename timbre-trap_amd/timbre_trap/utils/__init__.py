@@ -3,6 +3,10 @@
 device work), plus -- when a reference checkout is on ``sys.path`` after this package -- the reference's own host-only modules
 this package does not replace (``data``: constants / download helpers, ``visualization``), re-exported under the reference's
 names so that ``from timbre_trap.utils import *`` yields the same namespace as in the reference.
+
+``audio`` has no module of the same name in the reference: it holds what ``AudioDataset.get_audio`` asks of torchaudio and torch
+between a decoded file and the CQT (mono mix, sample-rate conversion, inf-norm) as device kernels -- ``resample``,
+``prepare_audio`` -- with the float64 host yardstick ``resample_host`` and the tap design ``sinc_resample_kernel``.
 """
 
 from pkgutil import extend_path
@@ -18,6 +22,7 @@ from .targets import multi_pitch_to_activations, activations_to_multi_pitch, hz_
 from .slicing import slice_audio, slice_times, resample_multi_pitch, nearest_indices, ExcerptSlicer
 from .metrics import (MultipitchEvaluator, multipitch_metrics, multipitch_metrics_device, multipitch_counts_device,
                       signal_distortion_ratio, signal_distortion_ratio_device, SignalDistortionRatio)
+from .audio import sinc_resample_kernel, resample_host, resample, mix_resample, prepare_audio
 from .trainloop import (make_schedulers, checkpoints_for, StepLogger, TrainingState, save_checkpoint, print_and_log,
                         log_gradient_norms, TRAIN_TAGS)
 
