@@ -157,7 +157,14 @@ int tt_cqt_generic_inverse(const tt_cqt_gplan* plan, const float* coeffs, float*
  *   transposed == 0 :  hi = ho*stride_h + kh*dil_h - pad_h
  *   transposed == 1 :  hi = (ho + pad_h - kh*dil_h) / stride_h   when divisible (else no term)
  * bias and res may be NULL.  Weight strides are signed (a flipped kernel = negative stride with
- * `w` pointing at the last tap). */
+ * `w` pointing at the last tap).
+ * res is added AFTER the activation, on every kernel behind this entry point (the model itself never passes one; the parity tests do).
+ * Alignment (all fp32 entry points of this section -- tt_conv2d, tt_conv2d_wgrad, tt_resblock_*, tt_sconv_*, tt_tconv_*,
+ * tt_channel_sum*): every pointer, scratch included, needs the 4-byte alignment of a float and nothing more.  The faster staging paths
+ * (LDS-DMA, 16-byte stores) are chosen per call where T % 4 == 0 and the pointers they touch are 16-byte aligned; any other call takes
+ * the register-staged kernels and returns the same results within rounding.  No call is refused for alignment.
+ * tests/test_gpu_conv_parity.py holds every element of these entry points to a derived rounding bound against float64, with each
+ * pointer in turn one float off a 16-byte boundary, planes down to 1 x 1, and NaN guard bands around every operand. */
 int tt_conv2d(const float* x, const float* w, const float* bias, const float* res, float* y,
               int B, int Cin, int Hin, int T, int Cout, int Hout,
               int KH, int KW, int stride_h, int dil_h, int dil_w, int pad_h, int pad_w,
@@ -167,7 +174,8 @@ int tt_conv2d(const float* x, const float* w, const float* bias, const float* re
 /* Weight + bias gradient of the same general convolution (transposed == 0 form):
  *   dw[co*ws_co + ci*ws_ci + kh*ws_kh + kw*ws_kw] += sum_{b,ho,t} g[b,co,ho,t] * x[b,ci,hi,ti]
  *   dbias[co] += sum g[b,co,:,:]          (dbias may be NULL)
- * Accumulates (+=) into dw/dbias: zero them first for a plain gradient. */
+ * Accumulates (+=) into dw/dbias: zero them first for a plain gradient.  (Partial sums meet in atomics: the low bits depend on the
+ * order of arrival once more than two workgroups add to an element.) */
 int tt_conv2d_wgrad(const float* x, const float* g, float* dw, float* dbias,
                     int B, int Cin, int Hin, int T, int Cout, int Hout,
                     int KH, int KW, int stride_h, int dil_h, int dil_w, int pad_h, int pad_w,
@@ -182,7 +190,9 @@ int tt_act_bwd(const float* dy, const float* y, float* g, int64_t n, int act, vo
 /* Fused ResidualConv2dBlock forward (modules.py:755-777):
  *   y = ELU(W2 . ELU(W1 (*)_dil x + b1) + b2) + x      x,y: (B,C,H,T), W1 (C,C,3,3), W2 (C,C,1,1)
  * Supported C: 4,8,16,32; dilation 1..3 (other widths: compose tt_conv2d calls).
- * If h1 != NULL the hidden activation ELU(W1 (*) x + b1) (B,C,H,T) is also written, for tt_resblock_bwd. */
+ * If h1 != NULL the hidden activation ELU(W1 (*) x + b1) (B,C,H,T) is also written, for tt_resblock_bwd; y is the same within
+ * rounding either way (not bit for bit: some kernels are chosen by the alignment of h1).  Planes smaller than the halo (H, T < dilation)
+ * are valid: taps outside the image contribute nothing. */
 int64_t tt_wgrad_scratch_floats(void);
 
 int tt_resblock_fwd(const float* x, const float* w1, const float* b1, const float* w2,
@@ -193,7 +203,8 @@ int tt_resblock_fwd(const float* x, const float* w1, const float* b1, const floa
  * recompute it from x (one more 3x3 convolution, half the saved-activation memory):
  *   inputs  x, h1, dy        outputs  dx (written), dw1/db1/dw2/db2 (accumulated, +=)
  * `ws` is scratch of B*C*H*T + tt_wgrad_scratch_floats() floats (dL/d(conv1 pre-activation), then the
- * per-workgroup partial weight gradients that a second launch sums without atomics). */
+ * per-workgroup partial weight gradients that a second launch sums without atomics); nothing beyond that size is touched.
+ * dx must not be NULL (TT_E_BADARG); what dx held is never read. */
 int tt_resblock_bwd(const float* x, const float* h1, const float* dy, const float* w1, const float* b1,
                     const float* w2, const float* b2, float* dx, float* dw1, float* db1,
                     float* dw2, float* db2, float* ws, int B, int C, int H, int T, int dilation,
@@ -375,7 +386,9 @@ int tt_convout16_1_bwd(const void* x, const float* y, const float* dy, const flo
 int tt_sconv_fwd(const float* x, const float* w, const float* b, float* y, int B, int C, int H, int T,
                  void* stream);
 /* Its backward from the saved input x and OUTPUT y: dx (written; may be NULL), dw / db (accumulated, +=);
- * `scratch` holds tt_wgrad_scratch_floats() + numel(dy) floats (reduction partials, then dy * ELU'(y)). */
+ * `scratch` holds tt_wgrad_scratch_floats() + numel(dy) floats (reduction partials, then dy * ELU'(y)).
+ * dx == NULL skips the data gradient only: dw and db are the same as with it.  With an odd H the last input row feeds no output
+ * row and its dx row is exactly 0.  H < 4: TT_E_BADARG.  The same holds for tt_tconv_bwd (H >= 1). */
 int tt_sconv_bwd(const float* x, const float* y, const float* dy, const float* w, float* dx, float* dw,
                  float* db, float* scratch, int B, int C, int H, int T, void* stream);
 

@@ -304,3 +304,76 @@ def test_four_pixel_narrow_forward_is_bit_identical(tmp_path):
         outs.append(out)
     r = subprocess.run([sys.executable, tool, 'cmp'] + outs, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and '0 differ' in r.stdout, r.stdout[-2000:]
+
+
+def _binding_cases():
+    """name, call(x, *params), x shape, parameter shapes.  Bitwise comparison needs sums that come out the same from run to run, and
+    several gradients of this path meet in atomics (waves of a workgroup in LDS, workgroups in memory).  Two addends commute, three
+    do not: the shapes keep every such meeting at two -- two rows (one wave each) per tile, two clips (one workgroup each) per call;
+    the per-workgroup partial weight gradients are added in a fixed order anyway.  The test checks that premise first."""
+    from timbre_trap.framework import ops
+    return [
+        ('residual_block C8', lambda x, *p: ops.residual_block(x, *p, 2), (2, 8, 2, 36), [(8, 8, 3, 3), (8,), (8, 8, 1, 1), (8,)]),
+        ('residual_block C16', lambda x, *p: ops.residual_block(x, *p, 3), (2, 16, 2, 36), [(16, 16, 3, 3), (16,), (16, 16, 1, 1), (16,)]),
+        ('conv', lambda x, w, b: ops.conv(x, w, b, ops.ConvCfg(3, 3, 1, 1, 1, 1, 'conv', 0, ops.ACT_ELU)), (2, 3, 1, 40), [(5, 3, 3, 3), (5,)]),
+        ('strided_conv', lambda x, w, b: ops.strided_conv(x, w, b, 4, 2), (2, 4, 6, 36), [(8, 4, 4, 1), (8,)]),
+        ('transposed_conv', lambda x, w, b: ops.transposed_conv(x, w, b, 4, 2, 1), (2, 8, 2, 36), [(8, 4, 4, 1), (4,)]),
+    ]
+
+
+def _strided_view_of(t):
+    """The same values as a non-contiguous view of a larger tensor (every other slice along the first dimension)."""
+    big = torch.full((2 * t.size(0),) + tuple(t.shape[1:]), 7.0, dtype=t.dtype, device=t.device)
+    big[::2] = t
+    v = big[::2]
+    assert not v.is_contiguous() and torch.equal(v, t)
+    return v
+
+
+@pytest.mark.parametrize('which', range(5), ids=['residual_block-C8', 'residual_block-C16', 'conv', 'strided_conv', 'transposed_conv'])
+def test_bindings_normalise_their_operands(which):
+    """The fp32 bindings hand raw data pointers to the library, which reads contiguous fp32.  A permuted input, a gradient that arrives
+    expanded (``y.sum().backward()``), parameters that are non-contiguous views of a larger tensor and float64 parameters must give,
+    bit for bit, what contiguous fp32 copies of the same values give (or raise TypeError / ValueError) -- never read the storage as if
+    it were contiguous fp32."""
+    name, call, xshape, pshapes = _binding_cases()[which]
+    x = _rand(*xshape, seed=1).cuda()
+    params = [_rand(*s, seed=2 + i, scale=0.3).cuda() for i, s in enumerate(pshapes)]
+
+    def run(xin, pin, expanded=False, gy=None):
+        leaves = [t.detach().requires_grad_(True) for t in [xin] + list(pin)]
+        y = call(*leaves)
+        if expanded:
+            y.sum().backward()
+        else:
+            y.backward(gy)
+        torch.cuda.synchronize()
+        return [y.detach()] + [t.grad for t in leaves]
+
+    gy = _rand(*run(x, params, expanded=True)[0].shape, seed=9).cuda()
+    base = run(x, params, gy=gy)
+    again = run(x, params, gy=gy)
+    assert all(torch.equal(a, b) for a, b in zip(base, again)), name + ': the baseline itself is not reproducible at this shape'
+    base_ones = run(x, params, gy=torch.ones_like(gy))
+
+    def same(got, want, what):
+        assert len(got) == len(want)
+        for i, (a, b) in enumerate(zip(got, want)):
+            assert a.shape == b.shape, (name, what, i)
+            assert torch.equal(a.double(), b.double()), '%s, %s: result %d differs from the contiguous fp32 call (max %.3e)' % (
+                name, what, i, float((a.double() - b.double()).abs().max()))
+
+    x_perm = x.transpose(0, 1).contiguous().transpose(0, 1)      # the same values, batch and channel strides swapped
+    assert not x_perm.is_contiguous() and torch.equal(x_perm, x)
+    variants = [
+        ('permuted x', lambda: run(x_perm, params, gy=gy), base),
+        ('expanded dy', lambda: run(x, params, expanded=True), base_ones),
+        ('strided parameters', lambda: run(x, [_strided_view_of(p) for p in params], gy=gy), base),
+        ('float64 parameters', lambda: run(x, [p.double() for p in params], gy=gy), base),
+    ]
+    for what, fn, want in variants:
+        try:
+            got = fn()
+        except (TypeError, ValueError):
+            continue
+        same(got, want, what)

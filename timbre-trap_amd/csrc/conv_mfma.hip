@@ -1967,7 +1967,7 @@ int sconv_bwd(const float* x, const float* y, const float* dy, const float* w, f
     int rc = 0;
     const long ng = (long)B * 2 * C * Hout * T;
     float* g = scratch + tt_wgrad_scratch_floats();
-    if (dma_ok(x, T) && dma_ok(dy, T) && dma_ok(g, T)) {
+    if (dma_ok(x, T) && dma_ok(dy, T) && dma_ok(g, T) && dma_ok(y, T)) {          // y: k_gate_and_sum reads it 16 bytes at a time
         (void)ng;
         hipLaunchKernelGGL(k_gate_and_sum, dim3(2 * C, gate_chunks(B, (long)Hout * T, 2 * C)), dim3(256), 0, st, dy, y, g, db, B,
                            2 * C, (long)Hout * T);
@@ -1993,7 +1993,7 @@ int tconv_bwd(const float* x, const float* y, const float* dy, const float* w, f
     int rc = 0;
     const long ng = (long)B * C * Hout * T;
     float* g = scratch + tt_wgrad_scratch_floats();
-    const bool dma = dma_ok(x, T) && dma_ok(dy, T) && dma_ok(g, T);
+    const bool dma = dma_ok(x, T) && dma_ok(dy, T) && dma_ok(g, T) && dma_ok(y, T);      // y: k_gate_and_sum reads it 16 bytes at a time
     if (dma) {
         (void)ng;
         hipLaunchKernelGGL(k_gate_and_sum, dim3(C, gate_chunks(B, (long)Hout * T, C)), dim3(256), 0, st, dy, y, g, db, B, C,

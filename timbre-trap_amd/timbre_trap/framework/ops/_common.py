@@ -82,6 +82,9 @@ def _off(t, elements):
 
 
 def _f32c(t):
+    """``t`` as the kernels read it: contiguous fp32 (``t`` itself when it already is; None stays None)."""
+    if t is None:
+        return None
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()

@@ -14,7 +14,8 @@ class ConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, cfg):
         _hip.require_cuda(x, w)
-        x, w = _f32c(x), _f32c(w)
+        params = (w, b)                                          # as given: _grad_target finds the flat gradient views through them
+        x, w, b = _f32c(x), _f32c(w), _f32c(b)                   # what the kernels read: contiguous fp32 (a no-op for the model's own tensors)
         B, Cin, Hin, T = x.shape
         KH, KW = cfg.KH, cfg.KW
         lib = _hip.lib()
@@ -34,7 +35,7 @@ class ConvFn(torch.autograd.Function):
                                 KH * KW, Cout * KH * KW, KW, 1, cfg.act, stream_ptr()), 'tt_conv2d(T)')
         ctx.cfg = cfg
         ctx.has_bias = b is not None
-        ctx.params = (w, b)
+        ctx.params = params
         ctx.save_for_backward(x, w, y if cfg.act != ACT_NONE else None)
         return y
 
@@ -148,7 +149,8 @@ class ResBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, dilation):
         _hip.require_cuda(x, w1)
-        x = _f32c(x)
+        params = (w1, b1, w2, b2)
+        x, w1, b1, w2, b2 = (_f32c(t) for t in (x, w1, b1, w2, b2))
         B, C, H, T = x.shape
         y = torch.empty_like(x)
         needs_grad = any(ctx.needs_input_grad[:5])
@@ -158,7 +160,7 @@ class ResBlockFn(torch.autograd.Function):
                                              _ops._flags(), stream_ptr()), 'tt_resblock_fwd')
         ctx.dilation = dilation
         ctx.flags = _ops._flags()
-        ctx.params = (w1, b1, w2, b2)
+        ctx.params = params
         ctx.save_for_backward(x, w1, b1, w2, b2, h1)
         return y
 
@@ -180,11 +182,12 @@ class ResBlockFn(torch.autograd.Function):
 def _stride_forward(ctx, entry, x, w, b, C, Cout, Hout, *extra):
     """StridedConvFn / TransposedConvFn forward on the MFMA strided kernels: C = channels of the narrow side; ``extra``: the out_pad of tt_tconv_*."""
     _hip.require_cuda(x, w)
-    x, w = _f32c(x), _f32c(w)
+    params = (w, b)
+    x, w, b = _f32c(x), _f32c(w), _f32c(b)
     B, _, H, T = x.shape
     y = torch.empty((B, Cout, Hout, T), dtype=torch.float32, device=x.device)
     check(getattr(_hip.lib(), entry + '_fwd')(ptr(x), ptr(w), ptr(b), ptr(y), B, C, H, T, *extra, stream_ptr()), entry + '_fwd')
-    ctx.params, ctx.geom = (w, b), (C, extra)
+    ctx.params, ctx.geom = params, (C, extra)
     ctx.save_for_backward(x, w, y)
     return y
 
