@@ -560,6 +560,14 @@ int tt_peak_pick(const float* x, float* out, int64_t n_outer, int F, int T, doub
 int tt_target_activations(const int* bins, const int* frames, int n, const double* weights, int radius, int F, int T,
                           double* work, double* out, void* stream);
 
+/* The same targets from note annotations (timbre_trap/datasets/NoteDataset.py:60-91: notes_to_multi_pitch, :93-123, followed by
+ * PitchDataset.multi_pitch_to_activations, PitchDataset.py:233-307; version 13): ones on row bins[i] over the frames lo[i] <= t < hi[i]
+ * (tt_note_spans' output, clipped to [0, T)) for every note i < L with 0 <= bins[i] < F -- a dropped note carries bin -1 -- then the
+ * blur, the division by the smallest blurred value over the painted positions and the clip of tt_target_activations.  Bit-identical to
+ * tt_target_activations on the expanded (bin, frame) pair list.  out, work: F*T doubles each (work unused when radius == 0). */
+int tt_target_activations_spans(const int* bins, const int* lo, const int* hi, int L, const double* weights, int radius, int F, int T,
+                                double* work, double* out, void* stream);
+
 /* ---- signal-distortion ratio (csrc/sdr.hip; version 10) ------------------------------------------------------------------------------
  * Replaces torchmetrics.audio.SignalDistortionRatio as built and called by experiments/evaluate.py:51,122-127
  * (`sdr_module(synth, audio).item()` per track, on the device, right after sliCQ.decode): the filtered SDR of B clips of N fp32
@@ -612,6 +620,28 @@ int tt_mpe_fill(const float* x, int F, int T, double threshold, int mode, int f_
 int tt_mpe_match(const int* est_idx, int n_ref_frames, int T, const int64_t* est_off, const int* est_bins, const double* est_midi,
                  int F, const int64_t* ref_off, const double* ref_midi, double window, int* tp, int* tp_chroma, int* n_est,
                  void* stream);
+
+/* ---- note annotations to per-frame lists (csrc/notes.hip; version 13) --------------------------------------------------------------
+ * Replaces NoteDataset.notes_to_multi_pitch (timbre_trap/datasets/NoteDataset.py:93-123: a Python loop over the L notes with an np.where
+ * over all N frames and an np.append per (note, frame) pair), as called per item from NoteDataset.py:81 and per track from
+ * experiments/evaluate.py:67-75, by flat arrays the device consumers read: frame ranges per note for tt_target_activations_spans, a CSR of
+ * note indices per frame for tt_mpe_match (gathered through a per-note MIDI table by the caller).  Nothing here uses atomics; every
+ * offset into the CSR is 64-bit; the results do not depend on the launch geometry.
+ *   tt_note_spans   (NoteDataset.py:119) times: N float64, NON-DECREASING (the caller checks); intervals: (L, 2) float64 onset / offset.
+ *                   lo[i], hi[i]: the half-open range of frames t with times[t] >= onset && times[t] < offset -- the reference's
+ *                   comparisons in float64, by binary search.  Empty (hi <= lo) when offset <= onset, when the note lies wholly before
+ *                   or after the grid, and (lo = hi = 0) when a bound is NaN
+ *   tt_note_tile_frames / tt_note_chunk   (NoteDataset.py:117-121) frames per workgroup of the two kernels below / notes they test
+ *                   against a tile per pass: the sizes at which their index arithmetic changes
+ *   tt_note_count   (NoteDataset.py:117-121) count[t] = number of notes i < L with lo[i] <= t < hi[i], t < N
+ *   tt_note_fill    (NoteDataset.py:117-121) note_idx[off[t] .. off[t + 1]) = those notes' indices in ASCENDING order -- the order in
+ *                   which the reference appends, so the gathered pitches equal its lists element for element; off[N + 1] is the
+ *                   exclusive prefix sum of tt_note_count's count (formed by the caller); nothing is written at or beyond `capacity` */
+int tt_note_tile_frames(void);
+int tt_note_chunk(void);
+int tt_note_spans(const double* times, int N, const double* intervals, int L, int* lo, int* hi, void* stream);
+int tt_note_count(const int* lo, const int* hi, int L, int N, int* count, void* stream);
+int tt_note_fill(const int* lo, const int* hi, int L, int N, const int64_t* off, int64_t capacity, int* note_idx, void* stream);
 
 /* ---- track audio: mono mix, sample-rate conversion, inf-norm (csrc/resample.hip; version 12) ----------------------------------------
  * Replaces the three lines of AudioDataset.get_audio (timbre_trap/datasets/AudioDataset.py:69-77) that stand between a decoded file

@@ -602,6 +602,87 @@ extern "C" int tt_target_activations(const int* bins, const int* frames, int n, 
     return 0;
 }
 
+// ---- the same targets from note annotations (reference NoteDataset.py:60-91: notes_to_multi_pitch, then multi_pitch_to_activations):
+// note i paints row bins[i] over the frames [lo[i], hi[i]) (tt_note_spans) instead of one (bin, frame) pair per launch lane; overlapping
+// notes store the same 1.0, so the painted map does not depend on the order of the stores.  The blur, the division and the clip are the
+// kernels above; the smallest blurred value over the painted positions is taken per workgroup and then over the workgroups' partials --
+// a minimum does not depend on the order either, so the result equals tt_target_activations' on the expanded pair list bit for bit.
+#define TGT_SPAN_PARTIALS 1024
+__device__ __forceinline__ bool tgt_span(const int* __restrict__ bins, const int* __restrict__ lo, const int* __restrict__ hi, int i, int F,
+                                         int T, int& f, int& t0, int& t1) {
+    f = bins[i];
+    t0 = lo[i] > 0 ? lo[i] : 0;
+    t1 = hi[i] < T ? hi[i] : T;
+    return f >= 0 && f < F && t0 < t1;                                   // dropped notes carry bin -1
+}
+__global__ __launch_bounds__(64) void k_tgt_paint(const int* __restrict__ bins, const int* __restrict__ lo, const int* __restrict__ hi, int F,
+                                                  int T, double* __restrict__ a) {
+    int f, t0, t1;
+    if (!tgt_span(bins, lo, hi, blockIdx.x, F, T, f, t0, t1)) return;
+    double* __restrict__ row = a + (long)f * T;
+    for (int t = t0 + threadIdx.x; t < t1; t += 64) row[t] = 1.0;
+}
+__device__ __forceinline__ double tgt_block_min(double m) {
+    __shared__ double red[256];
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) red[threadIdx.x] = fmin(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    return red[0];
+}
+// part[blockIdx.x] = smallest b over the spans of notes blockIdx.x, blockIdx.x + gridDim.x, ...
+__global__ __launch_bounds__(256) void k_tgt_span_min(const int* __restrict__ bins, const int* __restrict__ lo, const int* __restrict__ hi,
+                                                      int L, int F, int T, const double* __restrict__ b, double* __restrict__ part) {
+    double m = 1.0e300;
+    for (int i = blockIdx.x; i < L; i += gridDim.x) {
+        int f, t0, t1;
+        if (!tgt_span(bins, lo, hi, i, F, T, f, t0, t1)) continue;
+        const double* __restrict__ row = b + (long)f * T;
+        for (int t = t0 + threadIdx.x; t < t1; t += 256) m = fmin(m, row[t]);
+    }
+    m = tgt_block_min(m);
+    if (threadIdx.x == 0) part[blockIdx.x] = m;
+}
+// part[0] = smallest of part[0 .. n): one workgroup; every partial is read before the first barrier, part[0] is written after the last
+__global__ __launch_bounds__(256) void k_tgt_min_of_partials(double* __restrict__ part, int n) {
+    double m = 1.0e300;
+    for (int i = threadIdx.x; i < n; i += 256) m = fmin(m, part[i]);
+    m = tgt_block_min(m);
+    if (threadIdx.x == 0) part[0] = m;
+}
+
+extern "C" int tt_target_activations_spans(const int* bins, const int* lo, const int* hi, int L, const double* weights, int radius, int F,
+                                           int T, double* work, double* out, void* stream) {
+    if (!out || F <= 0 || T <= 0 || L < 0 || radius < 0 || (L > 0 && (!bins || !lo || !hi)) || (radius > 0 && (!weights || !work)))
+        return TT_E_BADARG;
+    hipStream_t st = tt_stream(stream);
+    const long total = (long)F * T;
+    double* seeds = radius > 0 ? work : out;
+    TT_HIP(hipMemsetAsync(seeds, 0, total * sizeof(double), st));
+    if (L == 0) {
+        if (radius > 0) TT_HIP(hipMemsetAsync(out, 0, total * sizeof(double), st));
+        return 0;
+    }
+    hipLaunchKernelGGL(k_tgt_paint, dim3(L), dim3(64), 0, st, bins, lo, hi, F, T, seeds);
+    TT_LAUNCH_CHECK();
+    if (radius == 0) return 0;
+    hipLaunchKernelGGL(k_tgt_blur, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const double*)work, weights, radius, F, T, out);
+    TT_LAUNCH_CHECK();
+    // the seeds are spent: work now holds the partial minima, min(L, TGT_SPAN_PARTIALS, F T) of them (work has F T doubles)
+    long parts = L < TGT_SPAN_PARTIALS ? L : TGT_SPAN_PARTIALS;
+    if (parts > total) parts = total;
+    hipLaunchKernelGGL(k_tgt_span_min, dim3((unsigned)parts), dim3(256), 0, st, bins, lo, hi, L, F, T, (const double*)out, work);
+    TT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_tgt_min_of_partials, dim3(1), dim3(256), 0, st, work, (int)parts);
+    TT_LAUNCH_CHECK();
+    // no painted position at all (every note dropped or empty): the map is zero and 0 / 1e300 = 0, tt_target_activations' n == 0 result
+    hipLaunchKernelGGL(k_tgt_normalise, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out, total, (const double*)work);
+    TT_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int tt_segment_stats(const float* x, const int64_t* offsets, int n_segments, float* out, void* stream) {
     if (!x || !offsets || !out || n_segments <= 0) return TT_E_BADARG;
     hipLaunchKernelGGL(k_segment_stats, dim3(n_segments), dim3(256), 0, tt_stream(stream), x, reinterpret_cast<const long*>(offsets), out);
@@ -632,7 +713,7 @@ extern "C" int tt_set_cu_limit(int cus) {
     return prev;
 }
 
-extern "C" int tt_version(void) { return 12; }   // 12: mono mix, sample-rate conversion and inf-norm of tracks (csrc/resample.hip: tt_resample*)   // 11: multi-pitch scoring on the device (csrc/mpe.hip: tt_mpe_*)   // 10: the device-side signal-distortion ratio (csrc/sdr.hip: tt_sdr_*)   // 9: split-operand training of the wide blocks (tt_x3_rb_fwd_train, tt_x3_rb_bwd, tt_x3_grad_scale, tt_x3_{pack,unpack}_scaled)   // 8: the magnitude variants (tt_cqt_forward_mag, tt_magnitude, tt_decibels, tt_act_bwd, TT_ACT_RELU / TT_ACT_SIGMOID, tt_activations1_*)   // 7: tt_channel_sum_ws (the channel sum in a fixed order)   // 6: tt_skip_join16_{fwd,bwd} (the skip joins of the 16-bit path in one pass each way)   // 5: gate links (tt_wide_level_bwd_gated, tt_*_bwd_pregated, tt_latent16_*_{gated,pregated}, tt_gate16)   // 4: any-block-length CQT, tt_set_loss_scale, tt_adamw_step(skipped)   // 3: bf16 channels-last entry points (tt_wide_*, tt_sconv16_*, tt_tconv16_*, tt_latent16_*, tt_conv{in,out}16_*)
+extern "C" int tt_version(void) { return 13; }   // 13: note annotations to per-frame lists and targets (csrc/notes.hip: tt_note_*; tt_target_activations_spans)   // 12: mono mix, sample-rate conversion and inf-norm of tracks (csrc/resample.hip: tt_resample*)   // 11: multi-pitch scoring on the device (csrc/mpe.hip: tt_mpe_*)   // 10: the device-side signal-distortion ratio (csrc/sdr.hip: tt_sdr_*)   // 9: split-operand training of the wide blocks (tt_x3_rb_fwd_train, tt_x3_rb_bwd, tt_x3_grad_scale, tt_x3_{pack,unpack}_scaled)   // 8: the magnitude variants (tt_cqt_forward_mag, tt_magnitude, tt_decibels, tt_act_bwd, TT_ACT_RELU / TT_ACT_SIGMOID, tt_activations1_*)   // 7: tt_channel_sum_ws (the channel sum in a fixed order)   // 6: tt_skip_join16_{fwd,bwd} (the skip joins of the 16-bit path in one pass each way)   // 5: gate links (tt_wide_level_bwd_gated, tt_*_bwd_pregated, tt_latent16_*_{gated,pregated}, tt_gate16)   // 4: any-block-length CQT, tt_set_loss_scale, tt_adamw_step(skipped)   // 3: bf16 channels-last entry points (tt_wide_*, tt_sconv16_*, tt_tconv16_*, tt_latent16_*, tt_conv{in,out}16_*)
 extern "C" const char* tt_arch(void) { return "gfx950"; }
 extern "C" const char* tt_error_string(int code) {
     if (code == 0) return "ok";

@@ -31,7 +31,9 @@ SOURCES = ['cqt.hip', 'cqt_generic.hip', 'conv_generic.hip', 'conv_mfma.hip', 'c
            # multi-pitch scores of evaluate(): compaction of the activation map and per-frame maximum matching
            'mpe.hip',
            # mono mix, sample-rate conversion and inf-norm of whole tracks (AudioDataset.get_audio)
-           'resample.hip']
+           'resample.hip',
+           # note annotations to frame ranges and per-frame note lists (NoteDataset.notes_to_multi_pitch)
+           'notes.hip']
 
 _lib = None
 
@@ -168,6 +170,7 @@ _PROTOS = {
     'tt_segment_stats': (c_int, [P, P, I, P, P]),
     'tt_peak_pick': (c_int, [P, P, L, I, I, ctypes.c_double, I, I, P]),
     'tt_target_activations': (c_int, [P, P, I, P, I, I, I, P, P, P]),
+    'tt_target_activations_spans': (c_int, [P, P, P, I, P, I, I, I, P, P, P]),
     'tt_sdr_chunk': (c_int, []),
     'tt_sdr_scratch_bytes': (c_int64, [I, L, I]),
     'tt_sdr_means': (c_int, [P, P, I, L, P, P, P]),
@@ -178,6 +181,11 @@ _PROTOS = {
     'tt_mpe_count': (c_int, [P, I, I, ctypes.c_double, I, I, P, P, P, P]),
     'tt_mpe_fill': (c_int, [P, I, I, ctypes.c_double, I, I, P, L, P, P]),
     'tt_mpe_match': (c_int, [P, I, I, P, P, P, I, P, P, ctypes.c_double, P, P, P, P]),
+    'tt_note_tile_frames': (c_int, []),
+    'tt_note_chunk': (c_int, []),
+    'tt_note_spans': (c_int, [P, I, P, I, P, P, P]),
+    'tt_note_count': (c_int, [P, P, I, I, P, P]),
+    'tt_note_fill': (c_int, [P, P, I, I, P, L, P, P]),
     'tt_resample_tile': (c_int, []),
     'tt_resample_direct_tile': (c_int, []),
     'tt_resample_max_taps': (c_int, []),

@@ -3,7 +3,7 @@
 section 6): when a reference checkout is on ``sys.path`` after this package, its dataset modules are used as they are -- this
 package's ``__path__`` is extended with the reference directory, so ``timbre_trap.datasets.MixedMultiPitch`` etc. resolve
 there and the base classes below are the reference's.  Without a reference checkout only the path-adjacent pieces exist
-(SURVEY.md section 8f, rows f3 / f4): the target helpers as static methods and the slicing arithmetic.
+(SURVEY.md section 8f, rows f3 / f4): the target and note helpers as static methods and the slicing arithmetic.
 """
 
 from pkgutil import extend_path
@@ -11,6 +11,7 @@ from pkgutil import extend_path
 __path__ = extend_path(__path__, __name__)
 
 from ..utils.audio import prepare_audio
+from ..utils.notes import notes_to_activations, notes_to_multi_pitch
 from ..utils.slicing import ExcerptSlicer
 from ..utils.targets import activations_to_multi_pitch, multi_pitch_to_activations
 
@@ -36,6 +37,16 @@ except Exception as _e:                          # no reference on the path, or 
 
         multi_pitch_to_activations = staticmethod(multi_pitch_to_activations)
         activations_to_multi_pitch = staticmethod(activations_to_multi_pitch)
+
+    class NoteDataset(PitchDataset):
+        """
+        Stand-in with the reference's static ``notes_to_multi_pitch(pitches, intervals, times)`` (``NoteDataset.py:93-123``; the
+        vectorised host function, same lists) and, as the static ``notes_to_activations``, the two lines of ``__getitem__`` that turn
+        a track's notes into its targets (``NoteDataset.py:81-84``) on the device.
+        """
+
+        notes_to_multi_pitch = staticmethod(notes_to_multi_pitch)
+        notes_to_activations = staticmethod(notes_to_activations)
 
     class AudioDataset(ExcerptSlicer):
         """

@@ -31,7 +31,8 @@ from .. import _hip
 from .targets import midi_to_hz
 
 __all__ = ['resample_multipitch', 'frequencies_to_midi', 'match_count', 'multipitch_metrics', 'MultipitchEvaluator',
-           'multipitch_counts_device', 'multipitch_metrics_device', 'mpe_compact', 'MPE_MAX_EST', 'MPE_MAX_REF',
+           'multipitch_counts_device', 'multipitch_metrics_device', 'multipitch_counts_device_notes',
+           'multipitch_metrics_device_notes', 'mpe_compact', 'MPE_MAX_EST', 'MPE_MAX_REF',
            'signal_distortion_ratio', 'signal_distortion_ratio_device', 'SignalDistortionRatio', 'SDR_CHUNK', 'SDR_MAX_FILTER']
 
 MAX_FREQ, MIN_FREQ = 5000.0, 20.0            # mir_eval.multipitch validation limits (evaluate.py:44-48 masks bins above 5 kHz)
@@ -219,6 +220,15 @@ class MultipitchEvaluator(object):
         return self._tagged(multipitch_metrics_device(times_ref, multi_pitch_ref, times_est, activations, midi_freqs,
                                                       window=self.tolerance, n_valid_bins=n_valid_bins))
 
+    def evaluate_notes(self, times_est, activations, midi_freqs, times_ref, pitches_hz, intervals, n_valid_bins=0):
+        """
+        ``evaluate_activations`` for a reference given as notes -- ``pitches_hz`` (L), ``intervals`` (L, 2) -- instead of frame lists:
+        the dictionary of ``evaluate_activations(..., times_ref, notes_to_multi_pitch(pitches_hz, intervals, times_ref))``, bit for
+        bit, with the reference lists built on the device too (reference ``experiments/evaluate.py:67-75,100-116`` on a ``NoteDataset``).
+        """
+        return self._tagged(multipitch_metrics_device_notes(times_ref, pitches_hz, intervals, times_est, activations, midi_freqs,
+                                                            window=self.tolerance, n_valid_bins=n_valid_bins))
+
 
 # ---- multi-pitch scores on the device (csrc/mpe.hip) -------------------------------------------------------------------------
 
@@ -336,22 +346,37 @@ def multipitch_counts_device(ref_time, ref_freqs, est_time, activations, midi_fr
     if midi_freqs.shape != (F,):
         raise ValueError('midi_freqs must hold one value per bin (%d), got shape %s' % (F, midi_freqs.shape))
     ref_off, ref_hz = _mpe_reference_csr(ref_freqs)
-    K = len(ref_time)
-    if K == 0 or T == 0 or F == 0:
-        empty = torch.zeros(K, dtype=torch.int32, device=dev)
-        return dict(tp=empty, tp_chroma=empty.clone(), n_ref=empty.clone(), n_est=empty.clone(), n_host_frames=0,
-                    sums=np.zeros(len(_MPE_SUMS), dtype=np.int64))
+    if len(ref_time) == 0 or T == 0 or F == 0:
+        return _mpe_no_counts(len(ref_time), dev)
+    ref_midi = frequencies_to_midi([ref_hz])[0]
+    return _mpe_counts_from_csr(x, ref_time, est_time, midi_freqs, torch.from_numpy(ref_off).to(dev), torch.from_numpy(ref_midi).to(dev),
+                                window, t, peaks_only, n_valid_bins)
+
+
+def _mpe_no_counts(K, dev):
+    empty = torch.zeros(K, dtype=torch.int32, device=dev)
+    return dict(tp=empty, tp_chroma=empty.clone(), n_ref=empty.clone(), n_est=empty.clone(), n_host_frames=0,
+                sums=np.zeros(len(_MPE_SUMS), dtype=np.int64))
+
+
+def _mpe_counts_from_csr(x, ref_time, est_time, midi_freqs, ref_off_d, ref_midi_d, window, t, peaks_only, n_valid_bins):
+    """
+    The device leg of ``multipitch_counts_device`` from a reference that is already a CSR on the device -- ``ref_off_d`` int64
+    [K + 1], ``ref_midi_d`` float64 MIDI numbers, range-checked by the caller -- and checked activations ``x`` (F, T) fp32 with
+    K, T, F >= 1.  The reference pitches of frames over a capacity, and only those, are read back for the host matcher.
+    """
+    F, T = x.shape
+    dev, K = x.device, len(ref_time)
     lib = _hip.lib()
     if (lib.tt_mpe_max_est(), lib.tt_mpe_max_ref()) != (MPE_MAX_EST, MPE_MAX_REF):
         raise RuntimeError('libttrap_hip.so was built with capacities (%d, %d), metrics says (%d, %d)'
                            % (lib.tt_mpe_max_est(), lib.tt_mpe_max_ref(), MPE_MAX_EST, MPE_MAX_REF))
-    ref_midi = frequencies_to_midi([ref_hz])[0]
     est_idx = _nearest_frame_index(est_time, ref_time, T).astype(np.int32)
     est_midi, bin_bad = _mpe_bin_tables(midi_freqs)
 
     est_off, est_bins, n_act, bad = mpe_compact(x, t, peaks_only, n_valid_bins, bin_bad)
-    ref_off_d = torch.from_numpy(ref_off).to(dev)
-    ref_midi_d = torch.from_numpy(ref_midi if ref_midi.size else np.zeros(1)).to(dev)
+    if ref_midi_d.numel() == 0:
+        ref_midi_d = torch.zeros(1, dtype=torch.float64, device=dev)
     est_idx_d = torch.from_numpy(est_idx).to(dev)
     est_midi_d = torch.from_numpy(est_midi).to(dev)
     tp = torch.empty(K, dtype=torch.int32, device=dev)
@@ -370,14 +395,14 @@ def multipitch_counts_device(ref_time, ref_freqs, est_time, activations, midi_fr
         raise ValueError('estimate frequencies must lie in [%g, %g] Hz' % (MIN_FREQ, MAX_FREQ))
     sums, n_host = back[:len(_MPE_SUMS)].copy(), int(back[-2])
     if n_host:
-        # over a capacity of the kernel: these frames alone are matched by the host function, from their own bins
+        # over a capacity of the kernel: these frames alone are matched by the host function, from their own bins and reference pitches
         js = torch.nonzero(flagged).flatten()
         fr = est_idx_d[js].to(torch.int64).clamp(max=T - 1)
-        spans = torch.stack([js, est_off[fr], est_off[fr + 1]], 1).cpu().numpy()
+        spans = torch.stack([js, est_off[fr], est_off[fr + 1], ref_off_d[js], ref_off_d[js + 1]], 1).cpu().numpy()
         got = np.zeros((n_host, 4), dtype=np.int64)
-        for row, (j, lo, hi) in zip(got, spans):
+        for row, (j, lo, hi, r_lo, r_hi) in zip(got, spans):
             bins = est_bins[lo:hi].cpu().numpy() if est_idx[j] < T else np.empty(0, dtype=np.int64)
-            r, e = ref_midi[ref_off[j]:ref_off[j + 1]], est_midi[bins]
+            r, e = ref_midi_d[r_lo:r_hi].cpu().numpy(), est_midi[bins]
             row[:] = (_max_matching(r, e, window, False), _max_matching(np.mod(r, 12), np.mod(e, 12), window, True), len(r), len(e))
         sums += np.array(_mpe_sums(got[:, 0], got[:, 1], got[:, 2], got[:, 3], np), dtype=np.int64)
         fix = torch.from_numpy(got.astype(np.int32)).to(dev)
@@ -391,6 +416,57 @@ def multipitch_metrics_device(ref_time, ref_freqs, est_time, activations, midi_f
     activations: see ``multipitch_counts_device``.  Empty ``ref_time`` or ``est_time`` give the all-zero dictionary.
     """
     counts = multipitch_counts_device(ref_time, ref_freqs, est_time, activations, midi_freqs, window, t, peaks_only, n_valid_bins)
+    return _scores_from_sums(counts['sums'])
+
+
+def multipitch_counts_device_notes(ref_time, pitches_hz, intervals, est_time, activations, midi_freqs, window=0.5, t=0.5, peaks_only=True,
+                                   n_valid_bins=0):
+    """
+    ``multipitch_counts_device(ref_time, notes_to_multi_pitch(pitches_hz, intervals, ref_time), ...)`` -- the same dictionary, bit for
+    bit -- for a reference given as notes (reference ``experiments/evaluate.py:67-75`` on a ``NoteDataset``): the per-frame reference
+    lists are never formed on the host.  The CSR of note indices is built on the device (csrc/notes.hip) and gathered through a
+    per-note MIDI table (``frequencies_to_midi`` over the L pitches); its total and two flags come back in one small copy.
+    ``ValueError`` as from the host route: ``pitches_hz`` / ``intervals`` length mismatch, a pitch outside [20, 5000] Hz of a note that
+    sounds in at least one frame (a silent note's pitch is never looked at, there as here).  ``ref_time`` that are not sorted take
+    the host lists.
+    """
+    from . import notes as _notes
+    pitches, intervals, ref_time = _notes._note_arrays(pitches_hz, intervals, ref_time)
+    if not _notes._is_sorted(ref_time):
+        return multipitch_counts_device(ref_time, _notes.notes_to_multi_pitch(pitches, intervals, ref_time), est_time, activations,
+                                        midi_freqs, window, t, peaks_only, n_valid_bins)
+    x = _mpe_activations(activations)
+    F, T = x.shape
+    dev = x.device
+    est_time = np.asarray(est_time, dtype=np.float64)
+    midi_freqs = np.asarray(midi_freqs, dtype=np.float64)
+    if len(est_time) != T:
+        raise ValueError('time and frequency lists must have the same number of frames')
+    if midi_freqs.shape != (F,):
+        raise ValueError('midi_freqs must hold one value per bin (%d), got shape %s' % (F, midi_freqs.shape))
+    K = len(ref_time)
+    lo, hi = _notes._device_spans(intervals, ref_time, dev)
+    # _mpe_reference_csr's range check, on the notes that sound: max() > MAX_FREQ or min() < MIN_FREQ over their pitches (a NaN among
+    # them makes both comparisons false)
+    sounding = hi > lo
+    outside = torch.from_numpy((pitches > MAX_FREQ) | (pitches < MIN_FREQ)).to(dev)
+    nan = torch.from_numpy(np.isnan(pitches)).to(dev)
+    ref_off_d, note_idx, (any_outside, any_nan) = _notes._device_csr(lo, hi, K, ((sounding & outside).any(), (sounding & nan).any()))
+    if any_outside and not any_nan:
+        raise ValueError('reference frequencies must lie in [%g, %g] Hz' % (MIN_FREQ, MAX_FREQ))
+    if K == 0 or T == 0 or F == 0:
+        return _mpe_no_counts(K, dev)
+    with np.errstate(divide='ignore', invalid='ignore'):                 # a silent note may carry any pitch, 0 included
+        note_midi = frequencies_to_midi([pitches])[0]
+    ref_midi_d = torch.from_numpy(note_midi).to(dev)[note_idx.to(torch.int64)]
+    return _mpe_counts_from_csr(x, ref_time, est_time, midi_freqs, ref_off_d, ref_midi_d, window, t, peaks_only, n_valid_bins)
+
+
+def multipitch_metrics_device_notes(ref_time, pitches_hz, intervals, est_time, activations, midi_freqs, window=0.5, t=0.5, peaks_only=True,
+                                    n_valid_bins=0):
+    """The fourteen scores of ``multipitch_metrics_device`` for a reference given as notes: see ``multipitch_counts_device_notes``."""
+    counts = multipitch_counts_device_notes(ref_time, pitches_hz, intervals, est_time, activations, midi_freqs, window, t, peaks_only,
+                                            n_valid_bins)
     return _scores_from_sums(counts['sums'])
 
 
