@@ -643,6 +643,42 @@ int tt_note_spans(const double* times, int N, const double* intervals, int L, in
 int tt_note_count(const int* lo, const int* hi, int L, int N, int* count, void* stream);
 int tt_note_fill(const int* lo, const int* hi, int L, int N, const int64_t* off, int64_t capacity, int* note_idx, void* stream);
 
+/* ---- frame-level pitch annotations to batched targets (csrc/pitch.hip; version 14) ---------------------------------------------------
+ * Replaces, per item of an MPEDataset, PitchDataset.resample_multi_pitch (timbre_trap/datasets/PitchDataset.py:194-231: interp1d over the
+ * track's frame times, then a list comprehension over the item's frames) followed by PitchDataset.multi_pitch_to_activations
+ * (PitchDataset.py:233-307) and the `.float()` of train.py:394, as PitchDataset.__getitem__ calls them (PitchDataset.py:164-192), for a
+ * whole batch in a number of launches that does not depend on the batch, from annotations that stay on the device:
+ *     times    float64, the source frame times of every track, concatenated; NON-DECREASING and finite within a track (the caller checks)
+ *     tracks   int64 [n_tracks][4] = {base, K, below, above}: track n's K frames are times[base .. base + K) and arena rows base .. base + K;
+ *              below / above (in [0, K)) are the frames that stand in for targets before / after the annotated span
+ *     row_off  int64, row_off[r] .. row_off[r + 1] are arena row r's values;  bins int32 per value: the nearest bin, -1 for a zero or
+ *              out-of-range pitch;  lost uint8 per row: the row holds a non-zero pitch outside the bin range
+ * Nothing here uses atomics; offsets into the arena and the output are 64-bit; no result depends on the launch geometry.
+ *   tt_pitch_tile_frames / tt_pitch_max_bins / tt_pitch_max_radius   (PitchDataset.py:233-307) frames per workgroup of tt_pitch_targets'
+ *                     kernels (the size at which their index arithmetic changes) and the capacities they hold: F <= max_bins,
+ *                     radius <= max_radius, else TT_E_BADARG
+ *   tt_pitch_scratch_bytes   (PitchDataset.py:233-307) bytes of `scratch` for tt_pitch_targets on B items of T frames
+ *   tt_pitch_nearest  (PitchDataset.py:213-229) idx[b][t] = the frame of track track[b] nearest to target[b][t] by the rule of
+ *                     interp1d(kind='nearest', assume_sorted=True, bounds_error=False, fill_value=(below, above)): the number of midpoints
+ *                     times[i] / 2 + times[i + 1] / 2 (float64, every operation rounded on its own) that are < target, by binary search;
+ *                     below for a target < times[0], above for one > times[K - 1] (-inf / +inf padding included); a NaN target sorts
+ *                     after every midpoint and fails both comparisons: K - 1.  -1 when track[b] is no track or the track is empty
+ *   tt_pitch_targets  (PitchDataset.py:233-307; train.py:394) out[b] (F, T), float64 or (out_float32 != 0) its round-to-nearest-even
+ *                     float32 cast: tt_target_activations on the (bin, frame) pairs of item b, whose frame t holds the values of arena
+ *                     row tracks[track[b]].base + idx[b][t] (an idx outside [0, K): none), bit for bit -- ones at the bins, then for
+ *                     radius > 0 the blur, the division by the smallest blurred value over the item's OWN painted positions, the clip;
+ *                     an item without a painted position is all zeros.  flags[b] = OR of lost[] over the rows item b reads (the warning
+ *                     of PitchDataset.py:280-283).  B <= 65535. */
+int     tt_pitch_tile_frames(void);
+int     tt_pitch_max_bins(void);
+int     tt_pitch_max_radius(void);
+int64_t tt_pitch_scratch_bytes(int B, int T);
+int tt_pitch_nearest(const double* times, const int64_t* tracks, int n_tracks, const int* track, const double* target, int B, int T,
+                     int* idx, void* stream);
+int tt_pitch_targets(const int* idx, const int64_t* tracks, int n_tracks, const int* track, int B, int T, const int64_t* row_off,
+                     const int* bins, const unsigned char* lost, const double* weights, int radius, int F, int out_float32, void* scratch,
+                     void* out, int* flags, void* stream);
+
 /* ---- track audio: mono mix, sample-rate conversion, inf-norm (csrc/resample.hip; version 12) ----------------------------------------
  * Replaces the three lines of AudioDataset.get_audio (timbre_trap/datasets/AudioDataset.py:69-77) that stand between a decoded file
  * and the CQT -- `torch.mean(audio, dim=0, keepdim=True)`, `torchaudio.functional.resample(audio, fs, self.sample_rate)`,

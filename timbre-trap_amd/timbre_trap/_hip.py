@@ -33,7 +33,9 @@ SOURCES = ['cqt.hip', 'cqt_generic.hip', 'conv_generic.hip', 'conv_mfma.hip', 'c
            # mono mix, sample-rate conversion and inf-norm of whole tracks (AudioDataset.get_audio)
            'resample.hip',
            # note annotations to frame ranges and per-frame note lists (NoteDataset.notes_to_multi_pitch)
-           'notes.hip']
+           'notes.hip',
+           # frame-level pitch annotations to batched targets (PitchDataset.resample_multi_pitch + multi_pitch_to_activations)
+           'pitch.hip']
 
 _lib = None
 
@@ -186,6 +188,12 @@ _PROTOS = {
     'tt_note_spans': (c_int, [P, I, P, I, P, P, P]),
     'tt_note_count': (c_int, [P, P, I, I, P, P]),
     'tt_note_fill': (c_int, [P, P, I, I, P, L, P, P]),
+    'tt_pitch_tile_frames': (c_int, []),
+    'tt_pitch_max_bins': (c_int, []),
+    'tt_pitch_max_radius': (c_int, []),
+    'tt_pitch_scratch_bytes': (c_int64, [I, I]),
+    'tt_pitch_nearest': (c_int, [P, P, I, P, P, I, I, P, P]),
+    'tt_pitch_targets': (c_int, [P, P, I, P, I, I, P, P, P, P, I, I, I, P, P, P, P]),
     'tt_resample_tile': (c_int, []),
     'tt_resample_direct_tile': (c_int, []),
     'tt_resample_max_taps': (c_int, []),

@@ -12,6 +12,7 @@ __path__ = extend_path(__path__, __name__)
 
 from ..utils.audio import prepare_audio
 from ..utils.notes import notes_to_activations, notes_to_multi_pitch
+from ..utils.pitch import pitch_to_activations
 from ..utils.slicing import ExcerptSlicer
 from ..utils.targets import activations_to_multi_pitch, multi_pitch_to_activations
 
@@ -32,10 +33,13 @@ except Exception as _e:                          # no reference on the path, or 
         """
         Stand-in with the reference's static target helpers (``PitchDataset.multi_pitch_to_activations`` /
         ``activations_to_multi_pitch``, device kernels) and slicing methods (``slice_times``, ``resample_multi_pitch``);
-        construct it with the CQT object and excerpt length instead of a dataset directory.
+        construct it with the CQT object and excerpt length instead of a dataset directory.  The static ``pitch_to_activations``
+        is the two lines of ``__getitem__`` that turn a track's annotations into an item's targets (``PitchDataset.py:182-185``)
+        on the device; ``utils.PitchBank`` does the same for whole batches from annotations uploaded once.
         """
 
         multi_pitch_to_activations = staticmethod(multi_pitch_to_activations)
+        pitch_to_activations = staticmethod(pitch_to_activations)
         activations_to_multi_pitch = staticmethod(activations_to_multi_pitch)
 
     class NoteDataset(PitchDataset):

@@ -22,8 +22,10 @@ from .targets import multi_pitch_to_activations, activations_to_multi_pitch, hz_
 from .slicing import slice_audio, slice_times, resample_multi_pitch, nearest_indices, ExcerptSlicer
 from .metrics import (MultipitchEvaluator, multipitch_metrics, multipitch_metrics_device, multipitch_counts_device,
                       multipitch_metrics_device_notes, multipitch_counts_device_notes,
+                      multipitch_metrics_device_track, multipitch_counts_device_track,
                       signal_distortion_ratio, signal_distortion_ratio_device, SignalDistortionRatio)
 from .notes import notes_to_multi_pitch, notes_csr_device, notes_to_activations, note_tiles
+from .pitch import PitchBank, pitch_to_activations, pitch_tiles
 from .audio import sinc_resample_kernel, resample_host, resample, mix_resample, prepare_audio
 from .trainloop import (make_schedulers, checkpoints_for, StepLogger, TrainingState, save_checkpoint, print_and_log,
                         log_gradient_norms, TRAIN_TAGS)

@@ -32,7 +32,7 @@ from .targets import midi_to_hz
 
 __all__ = ['resample_multipitch', 'frequencies_to_midi', 'match_count', 'multipitch_metrics', 'MultipitchEvaluator',
            'multipitch_counts_device', 'multipitch_metrics_device', 'multipitch_counts_device_notes',
-           'multipitch_metrics_device_notes', 'mpe_compact', 'MPE_MAX_EST', 'MPE_MAX_REF',
+           'multipitch_metrics_device_notes', 'multipitch_counts_device_track', 'multipitch_metrics_device_track', 'mpe_compact', 'MPE_MAX_EST', 'MPE_MAX_REF',
            'signal_distortion_ratio', 'signal_distortion_ratio_device', 'SignalDistortionRatio', 'SDR_CHUNK', 'SDR_MAX_FILTER']
 
 MAX_FREQ, MIN_FREQ = 5000.0, 20.0            # mir_eval.multipitch validation limits (evaluate.py:44-48 masks bins above 5 kHz)
@@ -228,6 +228,15 @@ class MultipitchEvaluator(object):
         """
         return self._tagged(multipitch_metrics_device_notes(times_ref, pitches_hz, intervals, times_est, activations, midi_freqs,
                                                             window=self.tolerance, n_valid_bins=n_valid_bins))
+
+    def evaluate_track(self, times_est, activations, midi_freqs, bank, track_id, n_valid_bins=0):
+        """
+        ``evaluate_activations`` for a reference kept on the device in a ``utils.pitch.PitchBank``: the dictionary of
+        ``evaluate_activations(..., *bank.tracks[track_id])``, bit for bit, without flattening and uploading the track's lists again
+        (reference ``experiments/evaluate.py:76-78,100-116`` on an ``MPEDataset``).
+        """
+        return self._tagged(multipitch_metrics_device_track(bank, track_id, times_est, activations, midi_freqs, window=self.tolerance,
+                                                            n_valid_bins=n_valid_bins))
 
 
 # ---- multi-pitch scores on the device (csrc/mpe.hip) -------------------------------------------------------------------------
@@ -467,6 +476,41 @@ def multipitch_metrics_device_notes(ref_time, pitches_hz, intervals, est_time, a
     """The fourteen scores of ``multipitch_metrics_device`` for a reference given as notes: see ``multipitch_counts_device_notes``."""
     counts = multipitch_counts_device_notes(ref_time, pitches_hz, intervals, est_time, activations, midi_freqs, window, t, peaks_only,
                                             n_valid_bins)
+    return _scores_from_sums(counts['sums'])
+
+
+def multipitch_counts_device_track(bank, track_id, est_time, activations, midi_freqs, window=0.5, t=0.5, peaks_only=True, n_valid_bins=0):
+    """
+    ``multipitch_counts_device(times, multi_pitch, ...)`` -- the same dictionary, bit for bit -- for the reference ``(times,
+    multi_pitch) = bank.tracks[track_id]`` of a ``utils.pitch.PitchBank`` (reference ``experiments/evaluate.py:76-78,116`` on an
+    ``MPEDataset``): the ragged lists are not flattened and uploaded again per call, the matching kernel reads the bank's row offsets
+    and MIDI numbers where they are.  ``ValueError`` as from the list route: estimate times / frames mismatch, a reference pitch
+    outside [20, 5000] Hz (found once, when the bank was built).
+    """
+    x = _mpe_activations(activations)
+    F, T = x.shape
+    est_time = np.asarray(est_time, dtype=np.float64)
+    midi_freqs = np.asarray(midi_freqs, dtype=np.float64)
+    if not 0 <= int(track_id) < len(bank):
+        raise IndexError('track id outside [0, %d)' % len(bank))
+    if x.device != bank.device:
+        raise RuntimeError('activations are on %s, the bank on %s' % (x.device, bank.device))
+    if len(est_time) != T:
+        raise ValueError('time and frequency lists must have the same number of frames')
+    if midi_freqs.shape != (F,):
+        raise ValueError('midi_freqs must hold one value per bin (%d), got shape %s' % (F, midi_freqs.shape))
+    if bank.host['outside'][track_id]:
+        raise ValueError('reference frequencies must lie in [%g, %g] Hz' % (MIN_FREQ, MAX_FREQ))
+    ref_time = bank.track_times(track_id)
+    if len(ref_time) == 0 or T == 0 or F == 0:
+        return _mpe_no_counts(len(ref_time), x.device)
+    ref_off_d, ref_midi_d = bank.reference_csr(track_id)
+    return _mpe_counts_from_csr(x, ref_time, est_time, midi_freqs, ref_off_d, ref_midi_d, window, t, peaks_only, n_valid_bins)
+
+
+def multipitch_metrics_device_track(bank, track_id, est_time, activations, midi_freqs, window=0.5, t=0.5, peaks_only=True, n_valid_bins=0):
+    """The fourteen scores of ``multipitch_metrics_device`` for a reference kept in a ``PitchBank``: see ``multipitch_counts_device_track``."""
+    counts = multipitch_counts_device_track(bank, track_id, est_time, activations, midi_freqs, window, t, peaks_only, n_valid_bins)
     return _scores_from_sums(counts['sums'])
 
 
