@@ -1129,7 +1129,18 @@ def test_skip_join_backward_riding_on_the_gated_level_stagewise(C, shape, reps):
                     arr([g_[0] for g_ in ga]), arr([g_[1] for g_ in ga]), arr([g_[2] for g_ in ga]), arr([g_[3] for g_ in ga]), ptr(ws), B, C, H, T, dils)
             if ride:
                 rc = lib.tt_wide_level_bwd_gated_join(*args, ptr(sg), reps, ptr(w), 3, ptr(ds), st)
-                assert rc == 0, rc
+                # the first block's kernel has a riding form on the default dispatch at every width; the A/B dispatches of
+                # test_separate_kernel_paths_still_agree take kernels without one: the level then says so (TT_W_JOIN_LEFT = 1) and the
+                # caller applies the join, as include/ttrap.h describes
+                if C <= 8:
+                    riding = os.environ.get('TTRAP_NARROW_FUSED16', '1') != '0'
+                elif lib.tt_wide_rb_bwd_is_onepass(C, 1):
+                    riding = C == 16
+                else:
+                    riding = os.environ.get('TTRAP_DXW', '1') != '0'
+                assert rc == (0 if riding else 1), (rc, riding)
+                if rc == 1:
+                    check(lib.tt_skip_join16_bwd(ptr(sg), ptr(xs[0]), ptr(w), 3, ptr(dx), ptr(ds), xs[0].numel(), reps, 3, st), 'join')
             else:
                 check(lib.tt_wide_level_bwd_gated(*args, st), 'level')
                 check(lib.tt_skip_join16_bwd(ptr(sg), ptr(xs[0]), ptr(w), 3, ptr(dx), ptr(ds), xs[0].numel(), reps, 3, st), 'join')
@@ -1145,6 +1156,150 @@ def test_skip_join_backward_riding_on_the_gated_level_stagewise(C, shape, reps):
     bad = (ctypes.c_int * 1)(2)
     assert lib.tt_wide_level_bwd_gated_join(1, arr(xs[:1]), arr(hs[:1]), ptr(dy), arr([par[0][0]]), arr([par[0][2]]), arr([par[0][3]]), ptr(dx), None, None,
                                             arr([ga[0][0]]), arr([ga[0][1]]), arr([ga[0][2]]), arr([ga[0][3]]), ptr(ws), B, C, H, T, bad, ptr(sg), reps, ptr(w), 3, ptr(ds), st) < 0
+
+
+def _grad_shapes(C):
+    return (C, C, 3, 3), (C,), (C, C, 1, 1), (C,)
+
+
+class _Level:
+    """A level of residual blocks run forward on the device, a gradient at its output and a gradient that reached the skip join on its
+    input: what the level backward entry points take, with fresh outputs per call."""
+
+    def __init__(self, C, shape, dil, reps=2):
+        from timbre_trap._hip import check, ptr, stream_ptr
+        lib, st = _lib(), stream_ptr()
+        B, H, T = shape
+        self.C, self.B, self.H, self.T, self.dil, self.reps, self.nb = C, B, H, T, dil, reps, len(dil)
+        self.par = [[_rand(C, C, 3, 3, seed=20 + i, scale=1.0 / (3 * C ** 0.5)).cuda(), _rand(C, seed=30 + i, scale=0.3).cuda(),
+                     _rand(C, C, 1, 1, seed=40 + i, scale=1.0 / C ** 0.5).cuda(), _rand(C, seed=50 + i, scale=0.3).cuda()] for i in range(self.nb)]
+        self.xs, self.hs = [self.nhwc() for _ in range(self.nb + 1)], [self.nhwc() for _ in range(self.nb)]
+        check(lib.tt_wide_pack(ptr(_rand(B, C, H, T, seed=1).cuda()), ptr(self.xs[0]), B, C, H, T, st), 'pack')
+        for i, p in enumerate(self.par):
+            check(lib.tt_wide_rb_fwd(ptr(self.xs[i]), ptr(p[0]), ptr(p[1]), ptr(p[2]), ptr(p[3]), ptr(self.xs[i + 1]), ptr(self.hs[i]), B, C, H, T, dil[i], st), 'fwd')
+        self.dy, self.sg = self.nhwc(), self.nhwc(reps * B)
+        check(lib.tt_wide_pack(ptr(_rand(B, C, H, T, seed=2).cuda()), ptr(self.dy), B, C, H, T, st), 'pack')
+        check(lib.tt_wide_pack(ptr(_rand(reps * B, C, H, T, seed=3, scale=0.7).cuda()), ptr(self.sg), reps * B, C, H, T, st), 'pack')
+        self.w = torch.tensor([0.5, -1.25, 2.0, 0.75, 1.5]).cuda()
+
+    def nhwc(self, b=None):
+        return torch.empty((b or self.B, self.H, self.T, self.C), dtype=ELT, device='cuda')
+
+    def outputs(self):
+        """dx, the gradients of every block (+= on top of 0.5), the skip weights' gradient (on top of 3), and the buffers a call needs besides."""
+        lib = _lib()
+        return dict(dx=self.nhwc(), grads=[[torch.full(s_, 0.5, device='cuda') for s_ in _grad_shapes(self.C)] for _ in range(self.nb)],
+                    ds=torch.full((5,), 3.0, device='cuda'), tmp=(self.nhwc(), self.nhwc()),
+                    ws=torch.zeros(lib.tt_wide_level_scratch_bytes(self.nb, self.B, self.C, self.H, self.T), dtype=torch.uint8, device='cuda'))
+
+    def call(self, out, st, join, dil=None):
+        """tt_wide_level_bwd (join = False) or tt_wide_level_bwd_gated_join onto `out` on stream `st` -> rc."""
+        import ctypes
+        from timbre_trap._hip import ptr
+        lib, nb = _lib(), self.nb
+        arr = lambda ts: (ctypes.c_void_p * nb)(*[t.data_ptr() for t in ts])
+        args = (nb, arr(self.xs[:nb]), arr(self.hs), ptr(self.dy), arr([p[0] for p in self.par]), arr([p[2] for p in self.par]), arr([p[3] for p in self.par]),
+                ptr(out['dx']), ptr(out['tmp'][0]), ptr(out['tmp'][1]), arr([g[0] for g in out['grads']]), arr([g[1] for g in out['grads']]),
+                arr([g[2] for g in out['grads']]), arr([g[3] for g in out['grads']]), ptr(out['ws']), self.B, self.C, self.H, self.T,
+                (ctypes.c_int * nb)(*(dil or self.dil)))
+        if join:
+            return lib.tt_wide_level_bwd_gated_join(*args, ptr(self.sg), self.reps, ptr(self.w), 3, ptr(out['ds']), st)
+        return lib.tt_wide_level_bwd(*args, st)
+
+
+def _same_weight_gradients(C, got, want, where):
+    """the bars of test_level_backward_equals_block_by_block: bit for bit, the narrow levels' 3x3 weight gradient at fp32 rounding."""
+    for j, name in enumerate(('dw1', 'db1', 'dw2', 'db2')):
+        if name == 'dw1' and C <= 8:
+            assert float((got[j] - want[j]).abs().max()) <= 1e-5 * float(want[j].abs().max()), (where, name)
+        else:
+            assert torch.equal(got[j], want[j]), (where, name)
+
+
+@pytest.mark.parametrize('C,shape', [(4, (1, 20, 66)), (16, (2, 21, 96)), (32, (1, 30, 160))])     # launch_nbwd, launch_bwds, launch_dxw
+def test_single_block_call_depends_on_its_arguments_only(C, shape):
+    """tt_wide_rb_bwd at dilation 1 -- the call a gated level with a riding join makes for its first block -- made from outside a level:
+    it reduces at once, and neither a finished nor a refused tt_wide_level_bwd_gated_join on the same thread changes what it computes
+    (dx bit for bit: ungated, no join term; the gradients at the bars of test_level_backward_equals_block_by_block)."""
+    from timbre_trap._hip import check, ptr, stream_ptr
+    lib, st = _lib(), stream_ptr()
+    B, H, T = shape
+    lv = _Level(C, shape, (1, 2, 3))
+    p = lv.par[0]
+
+    def single():
+        dx = torch.full((B, H, T, C), 0.5, dtype=ELT, device='cuda')
+        grads = [torch.full(s_, 0.5, device='cuda') for s_ in _grad_shapes(C)]
+        ws = torch.zeros(lib.tt_wide_scratch_bytes(B, C, H, T), dtype=torch.uint8, device='cuda')
+        check(lib.tt_wide_rb_bwd(ptr(lv.xs[0]), ptr(lv.hs[0]), ptr(lv.dy), ptr(p[0]), ptr(p[2]), ptr(p[3]), ptr(dx), ptr(grads[0]), ptr(grads[1]),
+                                 ptr(grads[2]), ptr(grads[3]), ptr(ws), B, C, H, T, 1, st), 'bwd')
+        torch.cuda.synchronize()
+        return dx, grads
+
+    dx0, g0 = single()
+    for t in [dx0] + g0:
+        assert not bool((t == 0.5).all()), 'the call left an output at its fill: the reduce did not run at once'
+    rc = lv.call(lv.outputs(), st, join=True)
+    assert rc in (0, 1), rc                                  # 1 = TT_W_JOIN_LEFT: an A/B dispatch without the riding form, the level ran all the same
+    torch.cuda.synchronize()
+    dx1, g1 = single()
+    assert lv.call(lv.outputs(), st, join=True, dil=(2, 2, 3)) < 0      # a first block at another dilation: refused
+    dx2, g2 = single()
+    for where, dx, g in (('after a level', dx1, g1), ('after a refused level', dx2, g2)):
+        assert torch.equal(dx, dx0), where
+        _same_weight_gradients(C, g, g0, where)
+
+
+def test_two_levels_in_flight_on_two_host_threads():
+    """Eight tt_wide_level_bwd_gated_join calls (C = 16) on one host thread and eight plain tt_wide_level_bwd calls (C = 4) on another, each
+    on its own stream, started together: every call returns 0 and gives what the same call gave alone -- dx bit for bit, the weight and
+    bias gradients at the bars of test_level_backward_equals_block_by_block, the skip weight's gradient (float atomics) to 1e-3."""
+    import ctypes
+    import threading
+    st0 = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    levels = [(_Level(16, (2, 21, 96), (1, 2, 3), reps=2), True), (_Level(4, (1, 20, 66), (1, 2, 3)), False)]
+    serial = []
+    for lv, join in levels:                                  # alone, one after the other (this also raises the kernels' LDS attributes)
+        out = lv.outputs()
+        assert lv.call(out, st0, join) == 0
+        serial.append(out)
+    outs = [[lv.outputs() for _ in range(8)] for lv, _ in levels]
+    streams = [torch.cuda.Stream() for _ in levels]
+    torch.cuda.synchronize()
+    barrier, rcs, errors = threading.Barrier(2), [[], []], []
+
+    def worker(k):
+        try:
+            lv, join = levels[k]
+            st = ctypes.c_void_p(streams[k].cuda_stream)
+            barrier.wait()
+            for out in outs[k]:
+                rcs[k].append(lv.call(out, st, join))
+            streams[k].synchronize()
+        except BaseException as e:                           # noqa: B902  (reported by the main thread)
+            errors.append(e)
+            barrier.abort()
+
+    threads = [threading.Thread(target=worker, args=(k,)) for k in range(2)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
+    torch.cuda.synchronize()
+    for k, (lv, join) in enumerate(levels):
+        assert rcs[k] == [0] * 8, rcs[k]
+        ref = serial[k]
+        for n, out in enumerate(outs[k]):
+            assert torch.equal(out['dx'], ref['dx']), (k, n)
+            for i in range(lv.nb):
+                _same_weight_gradients(lv.C, out['grads'][i], ref['grads'][i], (k, n, i))
+            ds0, ds1 = ref['ds'], out['ds']
+            assert torch.equal(ds0[[0, 1, 2, 4]], ds1[[0, 1, 2, 4]]) and float(ds0[0]) == 3.0
+            if join:
+                assert abs(float(ds1[3] - ds0[3])) <= 1e-3 * abs(float(ds0[3] - 3.0)) + 1e-3, (n, float(ds0[3]), float(ds1[3]))
+            else:
+                assert float(ds1[3]) == 3.0
 
 
 def _pytest_subprocess(env_extra, selection):
@@ -1188,5 +1343,6 @@ def test_fp16_build_passes_the_same_stagewise_tests():
     grids, bench heights, the gate links -- at the fp16 bars (2^-11 relative + 2.5e-4 of the tensor's scale per stored element)."""
     out = _pytest_subprocess(dict(TT_TEST_ELT='fp16', TT_CHILD_PYTEST='1'),
                              ['tests/test_gpu_wide_bf16.py', '-k', 'stagewise or multitile or edge_convs or capped_grids or bench_launch_shapes '
-                              'or bench_heights or skip_joins or skip_join or level_backward_equals or hands_the_layer'])
+                              'or bench_heights or skip_joins or skip_join or level_backward_equals or hands_the_layer or single_block_call_depends '
+                              'or two_levels_in_flight'])
     assert ' passed' in out

@@ -363,11 +363,10 @@ int launch_fused(const e16* x, const e16* dy, const float* w1, const float* b1, 
     e16x8* wimg = reinterpret_cast<e16x8*>(ws);
     float* part_a = reinterpret_cast<float*>(ws + K::IMG_BYTES);
     float* part_w = part_a + (long)MAX_W_WG * G::ADUMP;
-    if (!ttx_wprep_done) {                                       // inside tt_wide_level_bwd the images of all blocks were prepared in one launch
-        WPrep wp1{{w1}, {w2}, {wimg}};
-        hipLaunchKernelGGL(k_lvl_wprep<C>, dim3(K::NK * K::NCT + 1, 1), dim3(64), 0, st, wp1);
-        TT_LAUNCH_CHECK();
-    }
+    // never runs inside tt_wide_level_bwd (whose blocks take the kernels that use the saved h1): its own weight image, its reduce at once
+    WPrep wp1{{w1}, {w2}, {wimg}};
+    hipLaunchKernelGGL(k_lvl_wprep<C>, dim3(K::NK * K::NCT + 1, 1), dim3(64), 0, st, wp1);
+    TT_LAUNCH_CHECK();
     static AttrOnce once;
     auto kern = k_wrb_bwd_fused<C, D, TH, TW, NW>;
     if (int rc = raise_lds(kern, G::LDS_BYTES, once)) return rc;
@@ -380,7 +379,7 @@ int launch_fused(const e16* x, const e16* dy, const float* w1, const float* b1, 
     TT_LAUNCH_CHECK();
     RedArgs ra{part_w, grid, part_a, grid, dw1, db1, dw2, db2, C == 32 ? 1 : 0};
     constexpr int total = 9 * C * C + C * C + 2 * C;
-    return reduce_or_defer(k_wrb_reduce<C>, total, ra, st);
+    return reduce_or_defer(nullptr, k_wrb_reduce<C>, total, ra, st);
 }
 
 // Tile shapes (TTRAP_FBWD_TILE = 0 / 1 selects the alternative set, for tuning):
@@ -899,13 +898,13 @@ __global__ __launch_bounds__(NT, MINW) void k_wrb_bwds_sj(const e16* __restrict_
 
 template <int C, int D, int TH, int TW>
 int launch_bwds(const e16* x, const e16* h1, const e16* dy, const float* w1, const float* w2, const float* b2, e16* dx,
-                float* dw1, float* db1, float* dw2, float* db2, unsigned char* ws, int B, int H, int T, hipStream_t st) {
+                float* dw1, float* db1, float* dw2, float* db2, unsigned char* ws, int B, int H, int T, hipStream_t st, LevelCtx* ctx) {
     using G = OS<C, D, TH, TW>;
     using K = WK<C>;
     e16x8* wimg = reinterpret_cast<e16x8*>(ws);
     float* part_a = reinterpret_cast<float*>(ws + K::IMG_BYTES);
     float* part_w = part_a + (long)MAX_W_WG * G::ADUMP;
-    if (!ttx_wprep_done) {                                       // inside tt_wide_level_bwd the images of all blocks were prepared in one launch
+    if (!ctx || !ctx->wprep_done) {                              // a level prepares the images of all its blocks in one launch (LevelCtx)
         WPrep wp1{{w1}, {w2}, {wimg}};
         hipLaunchKernelGGL(k_lvl_wprep<C>, dim3(K::NK * K::NCT + 1, 1), dim3(64), 0, st, wp1);
         TT_LAUNCH_CHECK();
@@ -915,30 +914,23 @@ int launch_bwds(const e16* x, const e16* h1, const e16* dy, const float* w1, con
     static const int per_cu = tt_tune("TTRAP_BWDS_PER_CU", MINW);
     int grid = grid_for(nstrips, G::LDS_BYTES, per_cu);
     if (grid > MAX_W_WG) grid = MAX_W_WG;
-    bool gated = false;
-    if constexpr (D == 1) gated = ttx_gate_dx == 1;              // a level's first block: dx leaves gated
-    if (gated) {
-        if constexpr (D == 1) {
-            bool took = false;
+    const FirstForm form = first_form(ctx, D, C == 16);          // a level's first block: dx leaves gated; the riding form exists at C = 16 only
+    if constexpr (D == 1) {
+        if (form == FirstForm::Riding) {
             if constexpr (C == 16) {
-                if (ttx_skip.g) {
-                    static AttrOnce once_j;
-                    auto kj = k_wrb_bwds_sj<C, D, TH, TW, MINW>;
-                    if (int rc = raise_lds(kj, G::LDS_BYTES, once_j)) return rc;
-                    hipLaunchKernelGGL(kj, dim3(grid), dim3(NT), G::LDS_BYTES, st, x, h1, dy, wimg, b2, dx, part_a, part_w, B, H, T, tiles_t, nstrips, ttx_skip);
-                    ttx_skip.g = nullptr;
-                    took = true;
-                }
+                static AttrOnce once_j;
+                auto kj = k_wrb_bwds_sj<C, D, TH, TW, MINW>;
+                if (int rc = raise_lds(kj, G::LDS_BYTES, once_j)) return rc;
+                hipLaunchKernelGGL(kj, dim3(grid), dim3(NT), G::LDS_BYTES, st, x, h1, dy, wimg, b2, dx, part_a, part_w, B, H, T, tiles_t, nstrips, ctx->skip);
             }
-            if (!took) {
-                static AttrOnce once_g;
-                auto kg = k_wrb_bwds<C, D, TH, TW, MINW, true>;
-                if (int rc = raise_lds(kg, G::LDS_BYTES, once_g)) return rc;
-                hipLaunchKernelGGL(kg, dim3(grid), dim3(NT), G::LDS_BYTES, st, x, h1, dy, wimg, b2, dx, part_a, part_w, B, H, T, tiles_t, nstrips);
-            }
-            ttx_gate_dx = 2;
+        } else if (form == FirstForm::Gated) {
+            static AttrOnce once_g;
+            auto kg = k_wrb_bwds<C, D, TH, TW, MINW, true>;
+            if (int rc = raise_lds(kg, G::LDS_BYTES, once_g)) return rc;
+            hipLaunchKernelGGL(kg, dim3(grid), dim3(NT), G::LDS_BYTES, st, x, h1, dy, wimg, b2, dx, part_a, part_w, B, H, T, tiles_t, nstrips);
         }
-    } else {
+    }
+    if (form == FirstForm::Plain) {
         static AttrOnce once;
         auto kern = k_wrb_bwds<C, D, TH, TW, MINW, false>;
         if (int rc = raise_lds(kern, G::LDS_BYTES, once)) return rc;
@@ -947,13 +939,13 @@ int launch_bwds(const e16* x, const e16* h1, const e16* dy, const float* w1, con
     TT_LAUNCH_CHECK();
     RedArgs ra{part_w, grid, part_a, grid, dw1, db1, dw2, db2, C == 32 ? 1 : 0, C == 32 ? 0 : 1};
     constexpr int total = 9 * C * C + C * C + 2 * C;
-    return reduce_or_defer(k_wrb_reduce<C>, total, ra, st);
+    return reduce_or_defer(ctx, k_wrb_reduce<C>, total, ra, st);
 }
 
 template <int C>
 int bwds_c(const e16* x, const e16* h1, const e16* dy, const float* w1, const float* w2, const float* b2, e16* dx,
-           float* dw1, float* db1, float* dw2, float* db2, unsigned char* ws, int B, int H, int T, int D, hipStream_t st) {
-#define TT_BS(DD, TH_, TW_) return launch_bwds<C, DD, TH_, TW_>(x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, H, T, st)
+           float* dw1, float* db1, float* dw2, float* db2, unsigned char* ws, int B, int H, int T, int D, hipStream_t st, LevelCtx* ctx) {
+#define TT_BS(DD, TH_, TW_) return launch_bwds<C, DD, TH_, TW_>(x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, H, T, st, ctx)
     switch (D) {
         // 8-row steps everywhere.  C = 32 (round 4): 6-row steps at dilation 2, 3 fit a third workgroup per CU (46.9 / 53.3 KB of LDS) and
         // changed nothing at dilation 2 (0.458 ms either way) and lost at dilation 3 (0.637 vs 0.453 ms: the third workgroup does not
@@ -971,6 +963,20 @@ inline bool fshape_ok(int B, int C, int H, int T) {
 }
 
 }  // namespace
+
+// called by the block backward of conv_wide_bf16.hip with the context of the level it runs in (wide_common.h), by tt_wide_rb_bwd_onepass
+// with none; not part of the C ABI
+int ttx_wide_rb_bwd_onepass(LevelCtx* ctx, const void* x, const void* h1, const void* dy, const float* w1, const float* w2, const float* b2,
+                            void* dx, float* dw1, float* db1, float* dw2, float* db2, void* ws, int B, int C, int H, int T, int dilation,
+                            void* stream) {
+    if (!x || !h1 || !dy || !w1 || !w2 || !b2 || !dx || !dw1 || !db1 || !dw2 || !db2 || !ws) return TT_E_BADARG;
+    if (C != 16 && C != 32) return TT_E_UNSUPPORTED;
+    if (!fshape_ok(B, C, H, T)) return TT_E_BADARG;
+    const e16 *xi = (const e16*)x, *hi = (const e16*)h1, *gi = (const e16*)dy;
+    hipStream_t st = tt_stream(stream);
+    if (C == 16) return bwds_c<16>(xi, hi, gi, w1, w2, b2, (e16*)dx, dw1, db1, dw2, db2, (unsigned char*)ws, B, H, T, dilation, st, ctx);
+    return bwds_c<32>(xi, hi, gi, w1, w2, b2, (e16*)dx, dw1, db1, dw2, db2, (unsigned char*)ws, B, H, T, dilation, st, ctx);
+}
 
 // called by tt_wide_level_bwd (conv_wide_bf16.hip): the bf16 weight images of n blocks (image i at ws_i, where the one-pass kernels expect
 // it) in ONE launch; not part of the C ABI
@@ -1008,13 +1014,7 @@ int64_t tt_wide_onepass_scratch_bytes(int C) { return tt_wide_fused_scratch_byte
 int tt_wide_rb_bwd_onepass(const void* x, const void* h1, const void* dy, const float* w1, const float* w2, const float* b2, void* dx,
                            float* dw1, float* db1, float* dw2, float* db2, void* ws, int B, int C, int H, int T, int dilation,
                            void* stream) {
-    if (!x || !h1 || !dy || !w1 || !w2 || !b2 || !dx || !dw1 || !db1 || !dw2 || !db2 || !ws) return TT_E_BADARG;
-    if (C != 16 && C != 32) return TT_E_UNSUPPORTED;
-    if (!fshape_ok(B, C, H, T)) return TT_E_BADARG;
-    const e16 *xi = (const e16*)x, *hi = (const e16*)h1, *gi = (const e16*)dy;
-    hipStream_t st = tt_stream(stream);
-    if (C == 16) return bwds_c<16>(xi, hi, gi, w1, w2, b2, (e16*)dx, dw1, db1, dw2, db2, (unsigned char*)ws, B, H, T, dilation, st);
-    return bwds_c<32>(xi, hi, gi, w1, w2, b2, (e16*)dx, dw1, db1, dw2, db2, (unsigned char*)ws, B, H, T, dilation, st);
+    return ttx_wide_rb_bwd_onepass(nullptr, x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, C, H, T, dilation, stream);
 }
 
 }  // extern "C"

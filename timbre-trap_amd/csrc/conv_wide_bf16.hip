@@ -810,31 +810,27 @@ template <int C> constexpr long dump_floats() { return (long)MAX_A_WG * WA<C>::D
 
 template <int C, int D, int TH, int TW>
 int launch_dxw(const e16* x, const e16* da1, const e16* dy, const float* w1, e16* dx, float* part_w, float* part_a, int grid_a,
-               float* dw1, float* db1, float* dw2, float* db2, int B, int H, int T, hipStream_t st) {
+               float* dw1, float* db1, float* dw2, float* db2, int B, int H, int T, hipStream_t st, LevelCtx* ctx) {
     using X = DXW<C, D, TH, TW>;
     const int tiles_h = (H + TH - 1) / TH, tiles_t = (T + TW - 1) / TW, ntiles = B * tiles_h * tiles_t;
     static const int x_per_cu = tt_tune("TTRAP_DXW_PER_CU", C == 32 ? 3 : 4);      // registers: 165 / 113 VGPRs
     int gx = grid_for(ntiles, X::LDS_BYTES, x_per_cu);
     if (gx > MAX_W_WG) gx = MAX_W_WG;
-    bool gated = false;
-    if constexpr (D == 1) gated = ttx_gate_dx == 1;              // a level's first block: dx leaves gated (k_nrb_bwd_fused, GOUT)
-    if (gated) {
-        if constexpr (D == 1) {
-            if (ttx_skip.g) {
-                static AttrOnce once_j;
-                auto kj = k_wrb_dxw<C, D, TH, TW, true, true>;
-                if (int rc = raise_lds(kj, X::LDS_BYTES, once_j)) return rc;
-                hipLaunchKernelGGL(kj, dim3(gx), dim3(NT), X::LDS_BYTES, st, x, da1, dy, w1, dx, part_w, B, H, T, tiles_h, tiles_t, ntiles, ttx_skip);
-                ttx_skip.g = nullptr;
-            } else {
-                static AttrOnce once_g;
-                auto kg = k_wrb_dxw<C, D, TH, TW, true>;
-                if (int rc = raise_lds(kg, X::LDS_BYTES, once_g)) return rc;
-                hipLaunchKernelGGL(kg, dim3(gx), dim3(NT), X::LDS_BYTES, st, x, da1, dy, w1, dx, part_w, B, H, T, tiles_h, tiles_t, ntiles, SkipJ());
-            }
-            ttx_gate_dx = 2;
+    const FirstForm form = first_form(ctx, D, true);             // a level's first block: dx leaves gated (k_nrb_bwd_fused, GOUT)
+    if constexpr (D == 1) {
+        if (form == FirstForm::Riding) {
+            static AttrOnce once_j;
+            auto kj = k_wrb_dxw<C, D, TH, TW, true, true>;
+            if (int rc = raise_lds(kj, X::LDS_BYTES, once_j)) return rc;
+            hipLaunchKernelGGL(kj, dim3(gx), dim3(NT), X::LDS_BYTES, st, x, da1, dy, w1, dx, part_w, B, H, T, tiles_h, tiles_t, ntiles, ctx->skip);
+        } else if (form == FirstForm::Gated) {
+            static AttrOnce once_g;
+            auto kg = k_wrb_dxw<C, D, TH, TW, true>;
+            if (int rc = raise_lds(kg, X::LDS_BYTES, once_g)) return rc;
+            hipLaunchKernelGGL(kg, dim3(gx), dim3(NT), X::LDS_BYTES, st, x, da1, dy, w1, dx, part_w, B, H, T, tiles_h, tiles_t, ntiles, SkipJ());
         }
-    } else {
+    }
+    if (form == FirstForm::Plain) {
         static AttrOnce once_x;
         auto kx = k_wrb_dxw<C, D, TH, TW, false>;
         if (int rc = raise_lds(kx, X::LDS_BYTES, once_x)) return rc;
@@ -843,7 +839,7 @@ int launch_dxw(const e16* x, const e16* da1, const e16* dy, const float* w1, e16
     TT_LAUNCH_CHECK();
     RedArgs ra{part_w, gx, part_a, grid_a, dw1, db1, dw2, db2, C == 32 ? 1 : 0, C == 32 ? 0 : 1};
     constexpr int total = 9 * C * C + C * C + 2 * C;
-    return reduce_or_defer(k_wrb_reduce<C>, total, ra, st);
+    return reduce_or_defer(ctx, k_wrb_reduce<C>, total, ra, st);
 }
 
 // One-pass backward (k_wrb_bwds, conv_level_bf16.hip: column strips, dA1 in a rolling LDS ring, 4 tensors of HBM traffic) or the
@@ -865,8 +861,8 @@ inline int onepass_choice(int C, int D) {
 template <int C, int D>
 int launch_bwd(const e16* x, const e16* h1, const e16* dy, const float* w1, const float* w2, const float* b2,
                e16* dx, float* dw1, float* db1, float* dw2, float* db2, unsigned char* ws, int B, int H, int T,
-               hipStream_t st) {
-    if (onepass_choice(C, D)) return tt_wide_rb_bwd_onepass(x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, C, H, T, D, st);
+               hipStream_t st, LevelCtx* ctx) {
+    if (onepass_choice(C, D)) return ttx_wide_rb_bwd_onepass(ctx, x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, C, H, T, D, st);
     const long npix = (long)B * H * T;
     e16* da1 = reinterpret_cast<e16*>(ws);
     float* part_a = reinterpret_cast<float*>(ws + ((npix * C * 2 + 255) / 256) * 256);
@@ -893,7 +889,7 @@ int launch_bwd(const e16* x, const e16* h1, const e16* dy, const float* w1, cons
         // 0.456 -> 0.427 ms per call.  Dilation 3 (68 KB; 4-row tiles 49 KB): no change, 0.467 ms either way -- 8 rows kept.
         // Round 5: the x tile without halo: 8-row tiles fit three workgroups per CU at every dilation
         // (the round-3 / 4 form -- x with halo, 6-row tiles at C = 32 / dilation 2 -- is gone: profiles/r05_dxw_xh_x3n_shapes_ab.txt)
-        return launch_dxw<C, D, 8, 32>(x, da1, dy, w1, dx, part_w, part_a, grid, dw1, db1, dw2, db2, B, H, T, st);
+        return launch_dxw<C, D, 8, 32>(x, da1, dy, w1, dx, part_w, part_a, grid, dw1, db1, dw2, db2, B, H, T, st, ctx);
     }
     // data gradient
     if (int rc = launch_conv<C, D, 1, false>(da1, w1, nullptr, nullptr, nullptr, dy, dx, nullptr, B, H, T, st)) return rc;
@@ -910,7 +906,7 @@ int launch_bwd(const e16* x, const e16* h1, const e16* dy, const float* w1, cons
     TT_LAUNCH_CHECK();
     RedArgs ra{part_w, gw, part_a, grid, dw1, db1, dw2, db2};
     constexpr int total = 9 * C * C + C * C + 2 * C;
-    return reduce_or_defer(k_wrb_reduce<C>, total, ra, st);
+    return reduce_or_defer(ctx, k_wrb_reduce<C>, total, ra, st);
 }
 
 template <int C>
@@ -931,11 +927,12 @@ int fwd_c(const e16* x, const float* w1, const float* b1, const float* w2, const
 }
 template <int C>
 int bwd_c(const e16* x, const e16* h1, const e16* dy, const float* w1, const float* w2, const float* b2, e16* dx,
-          float* dw1, float* db1, float* dw2, float* db2, unsigned char* ws, int B, int H, int T, int D, hipStream_t st) {
+          float* dw1, float* db1, float* dw2, float* db2, unsigned char* ws, int B, int H, int T, int D, hipStream_t st,
+          LevelCtx* ctx) {
     switch (D) {
-        case 1: return launch_bwd<C, 1>(x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, H, T, st);
-        case 2: return launch_bwd<C, 2>(x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, H, T, st);
-        case 3: return launch_bwd<C, 3>(x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, H, T, st);
+        case 1: return launch_bwd<C, 1>(x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, H, T, st, ctx);
+        case 2: return launch_bwd<C, 2>(x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, H, T, st, ctx);
+        case 3: return launch_bwd<C, 3>(x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, H, T, st, ctx);
     }
     return TT_E_UNSUPPORTED;
 }
@@ -1827,7 +1824,7 @@ template <int C> constexpr long ndump_floats() { return (long)MAX_A_WG * (C * C 
 template <int C, int D>
 int launch_nbwd(const e16* x, const e16* h1, const e16* dy, const float* w1, const float* w2, const float* b2,
                 e16* dx, float* dw1, float* db1, float* dw2, float* db2, unsigned char* ws, int B, int H, int T,
-                hipStream_t st) {
+                hipStream_t st, LevelCtx* ctx) {
     const long npix = (long)B * H * T;
     e16* da1 = reinterpret_cast<e16*>(ws);
     float* part_a = reinterpret_cast<float*>(ws + ((npix * C * 2 + 255) / 256) * 256);
@@ -1844,25 +1841,21 @@ int launch_nbwd(const e16* x, const e16* h1, const e16* dy, const float* w1, con
         const int tiles_h = (H + F::TH - 1) / F::TH, tiles_t = (T + F::TW - 1) / F::TW, ntiles = B * tiles_h * tiles_t;
         int gf = grid_for(ntiles, LDS, 4);
         if (gf > MAX_W_WG) gf = MAX_W_WG;
-        bool gated = false;
-        if constexpr (D == 1) gated = ttx_gate_dx == 1;          // a level's first block (the reference's levels start at dilation 1)
-        if (gated) {
-            if constexpr (D == 1) {
-                if (ttx_skip.g) {
-                    static AttrOnce once_j;
-                    auto kj = k_nrb_bwd_fused<C, D, true, true>;
-                    if (int rc = raise_lds(kj, LDS, once_j)) return rc;
-                    hipLaunchKernelGGL(kj, dim3(gf), dim3(NT), LDS, st, x, h1, dy, w1, w2, b2, dx, part_a, part_w, B, H, T, tiles_h, tiles_t, ntiles, ttx_skip);
-                    ttx_skip.g = nullptr;
-                } else {
-                    static AttrOnce once_g;
-                    auto kg = k_nrb_bwd_fused<C, D, true>;
-                    if (int rc = raise_lds(kg, LDS, once_g)) return rc;
-                    hipLaunchKernelGGL(kg, dim3(gf), dim3(NT), LDS, st, x, h1, dy, w1, w2, b2, dx, part_a, part_w, B, H, T, tiles_h, tiles_t, ntiles, SkipJ());
-                }
-                ttx_gate_dx = 2;
+        const FirstForm form = first_form(ctx, D, true);         // a level's first block: dx leaves gated
+        if constexpr (D == 1) {
+            if (form == FirstForm::Riding) {
+                static AttrOnce once_j;
+                auto kj = k_nrb_bwd_fused<C, D, true, true>;
+                if (int rc = raise_lds(kj, LDS, once_j)) return rc;
+                hipLaunchKernelGGL(kj, dim3(gf), dim3(NT), LDS, st, x, h1, dy, w1, w2, b2, dx, part_a, part_w, B, H, T, tiles_h, tiles_t, ntiles, ctx->skip);
+            } else if (form == FirstForm::Gated) {
+                static AttrOnce once_g;
+                auto kg = k_nrb_bwd_fused<C, D, true>;
+                if (int rc = raise_lds(kg, LDS, once_g)) return rc;
+                hipLaunchKernelGGL(kg, dim3(gf), dim3(NT), LDS, st, x, h1, dy, w1, w2, b2, dx, part_a, part_w, B, H, T, tiles_h, tiles_t, ntiles, SkipJ());
             }
-        } else {
+        }
+        if (form == FirstForm::Plain) {
             static AttrOnce once_f;
             auto kf = k_nrb_bwd_fused<C, D, false>;
             if (int rc = raise_lds(kf, LDS, once_f)) return rc;
@@ -1871,7 +1864,7 @@ int launch_nbwd(const e16* x, const e16* h1, const e16* dy, const float* w1, con
         TT_LAUNCH_CHECK();
         RedArgs ra{part_w, gf, part_a, gf, dw1, db1, dw2, db2, 0, 1};
         constexpr int total = 9 * C * C + C * C + 2 * C;
-        return reduce_or_defer(k_nrb_reduce<C>, total, ra, st, NREL);
+        return reduce_or_defer(ctx, k_nrb_reduce<C>, total, ra, st, NREL);
     }
     const long ngroups = (npix + 63) / 64;
     const long want = (ngroups + 3) / 4;
@@ -1895,7 +1888,7 @@ int launch_nbwd(const e16* x, const e16* h1, const e16* dy, const float* w1, con
         TT_LAUNCH_CHECK();
         RedArgs ra{part_w, gx, part_a, grid, dw1, db1, dw2, db2, 0, 1};
         constexpr int total = 9 * C * C + C * C + 2 * C;
-        return reduce_or_defer(k_nrb_reduce<C>, total, ra, st, NREL);
+        return reduce_or_defer(ctx, k_nrb_reduce<C>, total, ra, st, NREL);
     }
     if (int rc = launch_nconv<C, D, 1, false>(da1, w1, nullptr, nullptr, nullptr, dy, dx, nullptr, B, H, T, st)) return rc;
     using W = NG<C, D>;
@@ -1910,7 +1903,7 @@ int launch_nbwd(const e16* x, const e16* h1, const e16* dy, const float* w1, con
     TT_LAUNCH_CHECK();
     RedArgs ra{part_w, gw, part_a, grid, dw1, db1, dw2, db2};
     constexpr int total = 9 * C * C + C * C + 2 * C;
-    return reduce_or_defer(k_nrb_reduce<C>, total, ra, st, NREL);
+    return reduce_or_defer(ctx, k_nrb_reduce<C>, total, ra, st, NREL);
 }
 
 template <int C>
@@ -1931,11 +1924,12 @@ int nfwd_c(const e16* x, const float* w1, const float* b1, const float* w2, cons
 }
 template <int C>
 int nbwd_c(const e16* x, const e16* h1, const e16* dy, const float* w1, const float* w2, const float* b2, e16* dx,
-           float* dw1, float* db1, float* dw2, float* db2, unsigned char* ws, int B, int H, int T, int D, hipStream_t st) {
+           float* dw1, float* db1, float* dw2, float* db2, unsigned char* ws, int B, int H, int T, int D, hipStream_t st,
+           LevelCtx* ctx) {
     switch (D) {
-        case 1: return launch_nbwd<C, 1>(x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, H, T, st);
-        case 2: return launch_nbwd<C, 2>(x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, H, T, st);
-        case 3: return launch_nbwd<C, 3>(x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, H, T, st);
+        case 1: return launch_nbwd<C, 1>(x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, H, T, st, ctx);
+        case 2: return launch_nbwd<C, 2>(x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, H, T, st, ctx);
+        case 3: return launch_nbwd<C, 3>(x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, H, T, st, ctx);
     }
     return TT_E_UNSUPPORTED;
 }
@@ -1946,7 +1940,8 @@ inline bool shape_ok(int B, int C, int H, int T) {
 }
 
 // dx *= ELU'(x) in place, 8 elements per thread step: what tt_wide_level_bwd_gated runs behind a first block whose backward kernel has no
-// gated form (a dilation other than 1, the A/B paths behind TTRAP_DXW / TTRAP_NARROW_FUSED16 / TTRAP_WBWD1)
+// gated form (a dilation other than 1, the A/B paths behind TTRAP_DXW / TTRAP_NARROW_FUSED16 / TTRAP_WBWD1): first_form
+// (wide_common.h) is then not asked or answers Plain, and the level's LevelCtx::gated stays false
 __global__ __launch_bounds__(256) void k_gate_dx(e16* __restrict__ dx, const e16* __restrict__ x, long n8) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
         e16x8 d = reinterpret_cast<const e16x8*>(dx)[i];
@@ -1958,11 +1953,6 @@ __global__ __launch_bounds__(256) void k_gate_dx(e16* __restrict__ dx, const e16
 }
 
 }  // namespace
-
-thread_local void* ttx_red_defer = nullptr;
-thread_local bool ttx_wprep_done = false;
-thread_local SkipJ ttx_skip;
-thread_local int ttx_gate_dx = 0;             // 1: the next block backward should leave dx * ELU'(x); 2: its kernel did (wide_common.h)
 
 extern "C" {
 
@@ -2040,9 +2030,9 @@ int tt_wide_rb_bwd_is_onepass(int C, int dilation) {
     return (C == 16 || C == 32) && dilation >= 1 && dilation <= 3 ? onepass_choice(C, dilation) : 0;
 }
 
-int tt_wide_rb_bwd(const void* x, const void* h1, const void* dy, const float* w1, const float* w2, const float* b2, void* dx,
-                   float* dw1, float* db1, float* dw2, float* db2, void* ws, int B, int C, int H, int T, int dilation,
-                   void* stream) {
+// tt_wide_rb_bwd with the calling level's context (nullptr: the public call)
+static int rb_bwd(LevelCtx* ctx, const void* x, const void* h1, const void* dy, const float* w1, const float* w2, const float* b2, void* dx,
+                  float* dw1, float* db1, float* dw2, float* db2, void* ws, int B, int C, int H, int T, int dilation, void* stream) {
     if (!x || !h1 || !dy || !w1 || !w2 || !b2 || !dx || !dw1 || !db1 || !dw2 || !db2 || !ws || !shape_ok(B, C, H, T))
         return TT_E_BADARG;
     const e16 *xi = (const e16*)x, *hi = (const e16*)h1, *gi = (const e16*)dy;
@@ -2050,11 +2040,17 @@ int tt_wide_rb_bwd(const void* x, const void* h1, const void* dy, const float* w
     unsigned char* w = (unsigned char*)ws;
     hipStream_t st = tt_stream(stream);
     switch (C) {
-        case 4: return nbwd_c<4>(xi, hi, gi, w1, w2, b2, go, dw1, db1, dw2, db2, w, B, H, T, dilation, st);
-        case 8: return nbwd_c<8>(xi, hi, gi, w1, w2, b2, go, dw1, db1, dw2, db2, w, B, H, T, dilation, st);
-        case 16: return bwd_c<16>(xi, hi, gi, w1, w2, b2, go, dw1, db1, dw2, db2, w, B, H, T, dilation, st);
+        case 4: return nbwd_c<4>(xi, hi, gi, w1, w2, b2, go, dw1, db1, dw2, db2, w, B, H, T, dilation, st, ctx);
+        case 8: return nbwd_c<8>(xi, hi, gi, w1, w2, b2, go, dw1, db1, dw2, db2, w, B, H, T, dilation, st, ctx);
+        case 16: return bwd_c<16>(xi, hi, gi, w1, w2, b2, go, dw1, db1, dw2, db2, w, B, H, T, dilation, st, ctx);
     }
-    return bwd_c<32>(xi, hi, gi, w1, w2, b2, go, dw1, db1, dw2, db2, w, B, H, T, dilation, st);
+    return bwd_c<32>(xi, hi, gi, w1, w2, b2, go, dw1, db1, dw2, db2, w, B, H, T, dilation, st, ctx);
+}
+
+int tt_wide_rb_bwd(const void* x, const void* h1, const void* dy, const float* w1, const float* w2, const float* b2, void* dx,
+                   float* dw1, float* db1, float* dw2, float* db2, void* ws, int B, int C, int H, int T, int dilation,
+                   void* stream) {
+    return rb_bwd(nullptr, x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, C, H, T, dilation, stream);
 }
 
 int64_t tt_wide_level_scratch_bytes(int nblocks, int B, int C, int H, int T) {
@@ -2062,16 +2058,20 @@ int64_t tt_wide_level_scratch_bytes(int nblocks, int B, int C, int H, int T) {
     return one < 0 || nblocks < 1 || nblocks > 4 ? -1 : (int64_t)nblocks * ((one + 255) / 256 * 256);
 }
 
-static int level_bwd(int gate, int nblocks, const void* const* x, const void* const* h1, const void* dy, const float* const* w1,
+// The level's backward: gate = leave dx * ELU'(x); skip.g = the skip-join backward to ride on the first block.  Returns TT_W_JOIN_LEFT when
+// that block took a kernel without the riding form (an A/B dispatch; C = 32 on the one-pass path).
+static int level_bwd(int gate, const SkipJ& skip, int nblocks, const void* const* x, const void* const* h1, const void* dy, const float* const* w1,
                      const float* const* w2, const float* const* b2, void* dx, void* tmp0, void* tmp1, float* const* dw1,
                      float* const* db1, float* const* dw2, float* const* db2, void* ws, int B, int C, int H, int T,
                      const int* dilations, void* stream) {
     if (nblocks < 1 || nblocks > 4 || !x || !h1 || !dy || !w1 || !w2 || !b2 || !dx || !dw1 || !db1 || !dw2 || !db2 || !ws || !dilations ||
         (nblocks > 1 && (!tmp0 || !tmp1)) || !shape_ok(B, C, H, T))
         return TT_E_BADARG;
-    if (ttx_red_defer) return TT_E_BADARG;                      // not re-entrant on one thread
     const int64_t one = (tt_wide_scratch_bytes(B, C, H, T) + 255) / 256 * 256;
     RedBatch batch;
+    LevelCtx ctx;
+    ctx.red = &batch;
+    ctx.skip = skip;
     int rc = 0;
     // the weight images of the blocks that take the one-pass kernel: one launch for the level
     {
@@ -2082,25 +2082,20 @@ static int level_bwd(int gate, int nblocks, const void* const* x, const void* co
             if (tt_wide_rb_bwd_is_onepass(C, dilations[i])) { pw1[np] = w1[i]; pw2[np] = w2[i]; pws[np] = (unsigned char*)ws + (int64_t)i * one; ++np; }
         if (np > 0) {
             if ((rc = ttx_wide_wprep_batch(C, np, pw1, pw2, pws, tt_stream(stream)))) return rc;
-            ttx_wprep_done = true;
+            ctx.wprep_done = true;
         }
     }
-    ttx_red_defer = &batch;
     const void* g = dy;
     for (int i = nblocks - 1; i >= 0 && !rc; --i) {
         void* gx = i == 0 ? dx : ((i & 1) ? tmp1 : tmp0);
-        ttx_gate_dx = (i == 0 && gate) ? 1 : 0;
-        rc = tt_wide_rb_bwd(x[i], h1[i], g, w1[i], w2[i], b2[i], gx, dw1[i], db1[i], dw2[i], db2[i], (unsigned char*)ws + (int64_t)i * one, B, C, H, T,
-                            dilations[i], stream);
+        ctx.gate = i == 0 && gate;
+        rc = rb_bwd(&ctx, x[i], h1[i], g, w1[i], w2[i], b2[i], gx, dw1[i], db1[i], dw2[i], db2[i], (unsigned char*)ws + (int64_t)i * one, B, C, H, T,
+                    dilations[i], stream);
         g = gx;
     }
-    const bool gate_left = ttx_gate_dx == 1;                    // asked for and not done by the first block's kernel
-    ttx_gate_dx = 0;
-    ttx_red_defer = nullptr;
-    ttx_wprep_done = false;
     if (rc) return rc;
     hipStream_t st = tt_stream(stream);
-    if (gate_left) {
+    if (gate && !ctx.gated) {                                    // asked for and not done by the first block's kernel
         const long n8 = (long)B * H * T * C / 8;                 // C * T is a multiple of 8 (shape_ok)
         const long want = (n8 + 255) / 256, cap = (long)8 * tt_cus();
         hipLaunchKernelGGL(k_gate_dx, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, st, (e16*)dx, (const e16*)x[0], n8);
@@ -2118,7 +2113,7 @@ static int level_bwd(int gate, int nblocks, const void* const* x, const void* co
         }
         TT_LAUNCH_CHECK();
     }
-    return 0;
+    return skip.g && !ctx.joined ? TT_W_JOIN_LEFT : 0;
 }
 
 int tt_gate16(void* g, const void* y, int64_t n, void* stream) {
@@ -2134,14 +2129,14 @@ int tt_wide_level_bwd(int nblocks, const void* const* x, const void* const* h1, 
                       const float* const* w2, const float* const* b2, void* dx, void* tmp0, void* tmp1, float* const* dw1,
                       float* const* db1, float* const* dw2, float* const* db2, void* ws, int B, int C, int H, int T,
                       const int* dilations, void* stream) {
-    return level_bwd(0, nblocks, x, h1, dy, w1, w2, b2, dx, tmp0, tmp1, dw1, db1, dw2, db2, ws, B, C, H, T, dilations, stream);
+    return level_bwd(0, SkipJ(), nblocks, x, h1, dy, w1, w2, b2, dx, tmp0, tmp1, dw1, db1, dw2, db2, ws, B, C, H, T, dilations, stream);
 }
 
 int tt_wide_level_bwd_gated(int nblocks, const void* const* x, const void* const* h1, const void* dy, const float* const* w1,
                             const float* const* w2, const float* const* b2, void* dx, void* tmp0, void* tmp1, float* const* dw1,
                             float* const* db1, float* const* dw2, float* const* db2, void* ws, int B, int C, int H, int T,
                             const int* dilations, void* stream) {
-    return level_bwd(1, nblocks, x, h1, dy, w1, w2, b2, dx, tmp0, tmp1, dw1, db1, dw2, db2, ws, B, C, H, T, dilations, stream);
+    return level_bwd(1, SkipJ(), nblocks, x, h1, dy, w1, w2, b2, dx, tmp0, tmp1, dw1, db1, dw2, db2, ws, B, C, H, T, dilations, stream);
 }
 
 int tt_wide_level_bwd_gated_join(int nblocks, const void* const* x, const void* const* h1, const void* dy, const float* const* w1,
@@ -2151,16 +2146,13 @@ int tt_wide_level_bwd_gated_join(int nblocks, const void* const* x, const void* 
                                  float* skip_dw, void* stream) {
     if (!skip_g || (skip_reps != 1 && skip_reps != 2) || skip_idx < 0 || !dilations || nblocks < 1) return TT_E_BADARG;
     if (dilations[0] != 1) return TT_E_UNSUPPORTED;              // only a first block at dilation 1 has a gated epilogue (the reference's levels)
-    ttx_skip.g = (const e16*)skip_g;
-    ttx_skip.half = skip_reps == 2 ? (long)B * H * T * C : 0;
-    ttx_skip.w = skip_weights ? skip_weights + skip_idx : nullptr;
-    ttx_skip.dw = skip_dw ? skip_dw + skip_idx : nullptr;
-    ttx_skip.unscale = tt_loss_unscale();
-    const int rc = level_bwd(1, nblocks, x, h1, dy, w1, w2, b2, dx, tmp0, tmp1, dw1, db1, dw2, db2, ws, B, C, H, T, dilations, stream);
-    const bool left = ttx_skip.g != nullptr;                     // the first block took a kernel without the riding form (an A/B dispatch)
-    ttx_skip = SkipJ();
-    if (rc) return rc;
-    return left ? TT_W_JOIN_LEFT : 0;
+    SkipJ skip;
+    skip.g = (const e16*)skip_g;
+    skip.half = skip_reps == 2 ? (long)B * H * T * C : 0;
+    skip.w = skip_weights ? skip_weights + skip_idx : nullptr;
+    skip.dw = skip_dw ? skip_dw + skip_idx : nullptr;
+    skip.unscale = tt_loss_unscale();
+    return level_bwd(1, skip, nblocks, x, h1, dy, w1, w2, b2, dx, tmp0, tmp1, dw1, db1, dw2, db2, ws, B, C, H, T, dilations, stream);
 }
 
 }  // extern "C"

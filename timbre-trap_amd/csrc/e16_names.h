@@ -32,10 +32,8 @@
 #define tt_convin16_1_bwd tt_convin16_1_bwd_h
 #define tt_convout16_1_fwd tt_convout16_1_fwd_h
 #define tt_convout16_1_bwd tt_convout16_1_bwd_h
-#define ttx_red_defer ttx_red_defer_h
-#define ttx_wprep_done ttx_wprep_done_h
-#define ttx_gate_dx ttx_gate_dx_h
-#define ttx_skip ttx_skip_h
+#define LevelCtx LevelCtx_h
+#define ttx_wide_rb_bwd_onepass ttx_wide_rb_bwd_onepass_h
 #define tt_wide_level_bwd_gated_join tt_wide_level_bwd_gated_join_h
 #define ttx_wide_wprep_batch ttx_wide_wprep_batch_h
 #define tt_wide_level_bwd tt_wide_level_bwd_h

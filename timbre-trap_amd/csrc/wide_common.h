@@ -123,8 +123,6 @@ __global__ __launch_bounds__(1024) void k_wrb_reduce(RedBatch batch) {
     }
 }
 
-// Where a launcher would start its reduce: now, or -- inside tt_wide_level_bwd -- into the level's batch (ttx_red_defer: the calling
-// thread's pending batch; conv_wide_bf16.hip defines it, conv_level_bf16.hip's launchers see it too).
 }  // namespace
 // The backward of a weighted skip join riding on a level's gated first block (round 6; tt_wide_level_bwd_gated_join): the block's x IS the
 // encoder embedding e of the join, so its GOUT epilogue -- which has x at hand for ELU'(x) -- also takes the embedding's share of the join's
@@ -140,11 +138,22 @@ struct SkipJ {
     float* dw = nullptr;           // &d skip_weights[idx] (nullptr: not wanted)
     float unscale = 1.f;           // 1 / loss scale (dw leaves the 16-bit region)
 };
-extern thread_local SkipJ ttx_skip;         // set by tt_wide_level_bwd_gated_join; the launch that takes it resets .g
-extern thread_local void* ttx_red_defer;
-extern thread_local int ttx_gate_dx;        // set by tt_wide_level_bwd_gated around its first block: 1 = asked for, 2 = the block's kernel gated dx
-extern thread_local bool ttx_wprep_done;     // set by tt_wide_level_bwd while the weight images of its blocks are already prepared
+// What one tt_wide_level_bwd* call tells the block launchers below it, and what they tell it back.  The level keeps one on its stack and
+// hands a pointer down through the block backward to the launcher (conv_wide_bf16.hip, and across to conv_level_bf16.hip for the one-pass
+// kernels); the public single-block entry points pass nullptr: reduce now, prepare your own weight image, no gating, no join.
+struct LevelCtx {
+    void* red = nullptr;           // the level's RedBatch (opaque here: RedBatch is local to each translation unit): reduces go into it
+    bool wprep_done = false;       // the weight images of the level's one-pass blocks were prepared in one launch
+    bool gate = false;             // the block being called is the level's first and should leave dx * ELU'(x)
+    SkipJ skip;                    // the skip-join backward that may ride on that block's epilogue (.g == nullptr: none)
+    bool gated = false;            // out: the first block's kernel gated dx (otherwise k_gate_dx runs behind the level)
+    bool joined = false;           // out: ... and took the join (otherwise TT_W_JOIN_LEFT)
+};
 int ttx_wide_wprep_batch(int C, int n, const float* const* w1, const float* const* w2, void* const* ws, hipStream_t st);
+// tt_wide_rb_bwd_onepass with the calling level's context (nullptr: the public call)
+int ttx_wide_rb_bwd_onepass(LevelCtx* ctx, const void* x, const void* h1, const void* dy, const float* w1, const float* w2, const float* b2,
+                            void* dx, float* dw1, float* db1, float* dw2, float* db2, void* ws, int B, int C, int H, int T, int dilation,
+                            void* stream);
 namespace {
 // the per-lane pieces of that epilogue: t[j] = g0[j] + g1[j]; acc += <t, x>; returns w * t[j] through `add`
 template <class V, int N>
@@ -163,9 +172,22 @@ __device__ __forceinline__ void skipj_finish(float dot, const SkipJ& sj) {
     if ((threadIdx.x & 63) == 0) atomicAdd(sj.dw, dot * sj.unscale);
 }
 
-template <class Kernel> inline int reduce_or_defer(Kernel kern, int total, const RedArgs& ra, hipStream_t st, int per_block = REL) {
-    if (ttx_red_defer) {
-        RedBatch* b = static_cast<RedBatch*>(ttx_red_defer);
+// Which form of its kernel a block backward launches: the gated and riding forms exist for a level's first block at dilation 1 only (the
+// reference's levels start there), the riding form not in every launcher.  Notes the choice in the context: that is how the level learns
+// whether the gate and the join are still to be done.
+enum class FirstForm { Plain, Gated, Riding };
+inline FirstForm first_form(LevelCtx* ctx, int D, bool has_riding) {
+    if (!ctx || !ctx->gate || D != 1) return FirstForm::Plain;
+    ctx->gated = true;
+    if (!has_riding || !ctx->skip.g) return FirstForm::Gated;
+    ctx->joined = true;
+    return FirstForm::Riding;
+}
+
+// Where a launcher starts its reduce: now, or -- inside tt_wide_level_bwd -- into the level's batch
+template <class Kernel> inline int reduce_or_defer(LevelCtx* ctx, Kernel kern, int total, const RedArgs& ra, hipStream_t st, int per_block = REL) {
+    if (ctx && ctx->red) {
+        RedBatch* b = static_cast<RedBatch*>(ctx->red);
         if (b->n >= 4) return TT_E_BADARG;
         b->a[b->n++] = ra;
         return 0;

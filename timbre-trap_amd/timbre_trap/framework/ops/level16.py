@@ -76,8 +76,6 @@ def _level16_backward(ctx, dy):
         jidx, jlink, jparam, jdefer = ctx.join
         de, rs = _skip._join_backward(g_all, je, jw, jidx, B // je.size(0), jlink, jparam, ctx.needs_input_grad[3], ctx.needs_input_grad[4], jdefer)
     recompute = ctx.recompute
-    ws_bytes = lib.tt_wide_fused_scratch_bytes(C) if recompute else lib.tt_wide_scratch_bytes(B, C, H, T)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g_all.device)
     targets = [_grad_target(t) for t in ctx.params]
     dx = new_cl16(B, C, H, T, g_all.device, dt)
     tmp = [new_cl16(B, C, H, T, g_all.device, dt) for _ in range(2)] if nb > 1 else []
@@ -110,6 +108,8 @@ def _level16_backward(ctx, dy):
         return dx, [r for _, r in targets], de, rs
     if ctx.gate:
         raise RuntimeError('ops.LEVEL_BWD / RECOMPUTE_CHANNELS changed between the forward and the backward of a level')
+    ws_bytes = lib.tt_wide_fused_scratch_bytes(C) if recompute else lib.tt_wide_scratch_bytes(B, C, H, T)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g_all.device)
     g = g_all
     for i in reversed(range(nb)):
         w1, b1_, w2, b2 = params[4 * i: 4 * i + 4]
