@@ -292,6 +292,16 @@ int tt_wide_rb_bwd_onepass(const void* x, const void* h1, const void* dy, const 
                            void* dx, float* dw1, float* db1, float* dw2, float* db2, void* ws, int B, int C, int H, int T,
                            int dilation, void* stream);
 int tt_wide_rb_bwd_is_onepass(int C, int dilation);
+/* What the loaded code object holds for one of the block-backward kernels (version 15; diagnostic, no launch, needs a device):
+ * *local_bytes = private (scratch) memory per lane -- stack objects and register spills, 0 for a kernel that keeps everything in
+ * registers -- and *num_regs = its vector registers (hipFuncAttributes::localSizeBytes / numRegs).  kernel: TT_BWD_KERNEL_STRIPS
+ * (k_wrb_bwds, C = 16 / 32), TT_BWD_KERNEL_DXW (k_wrb_dxw, C = 16 / 32), TT_BWD_KERNEL_NARROW (k_nrb_bwd_fused, C = 4 / 8); dilation
+ * 1..3; form 0 = plain, 1 = gated, 2 = riding (a skip join on the gated epilogue) -- the last two exist at dilation 1 only, the riding
+ * strips at C = 16 only.  TT_E_UNSUPPORTED for a combination that is not compiled; > 0: the hipError_t of the attribute query. */
+#define TT_BWD_KERNEL_STRIPS 0
+#define TT_BWD_KERNEL_DXW    1
+#define TT_BWD_KERNEL_NARROW 2
+int tt_wide_bwd_kernel_attr(int kernel, int C, int dilation, int form, int* local_bytes, int* num_regs);
 
 /* bf16 channel-innermost (4,1) strided / transposed layers between the levels (csrc/conv_stride_bf16.hip): the bf16-storage
  * counterparts of tt_sconv_* / tt_tconv_* below.  x, y, dy, dx are bf16 [B][H][T][channels]; w (2C, C, 4, 1), b and their
@@ -838,6 +848,7 @@ int tt_wide_rb_bwd_onepass_h(const void* x, const void* h1, const void* dy, cons
                            void* dx, float* dw1, float* db1, float* dw2, float* db2, void* ws, int B, int C, int H, int T,
                            int dilation, void* stream);
 int tt_wide_rb_bwd_is_onepass_h(int C, int dilation);
+int tt_wide_bwd_kernel_attr_h(int kernel, int C, int dilation, int form, int* local_bytes, int* num_regs);
 int64_t tt_stride16_scratch_bytes_h(int C);
 int tt_sconv16_fwd_h(const void* x, const float* w, const float* b, void* y, int B, int C, int H, int T, void* stream);
 int tt_sconv16_bwd_h(const void* x, const void* y, const void* dy, const float* w, void* dx, float* dw, float* db, void* ws,

@@ -470,9 +470,12 @@ template <int C, int D, int TH, int TW> struct OS {
     static_assert(TH >= D, "a step must reach the rows the next one needs");
 };
 
-// 3x3 dilated product on one 16-pixel group out of the ring: `ro[kh]` = byte offset of the image row of tap row kh
+// 3x3 dilated product on one 16-pixel group out of the ring: `ro0 / ro1 / ro2` = byte offset of the image row of tap row 0 / 1 / 2.
+// Three scalars BY VALUE: at C = 16 the tap row depends on the lane, and a select chain over a by-reference array became a two-entry
+// private array -- a store to scratch and a dependent per-lane load from it in front of every group's first product, with the full
+// vmcnt(0) that goes with it (ScratchSize 16 in a kernel the register report calls spill-free: a stack object is not a spill).
 template <int C, int D, int IW>
-__device__ __forceinline__ void conv_taps_ring(const unsigned char* img, const int (&ro)[3], int col, int g,
+__device__ __forceinline__ void conv_taps_ring(const unsigned char* img, int ro0, int ro1, int ro2, int col, int g,
                                                const e16x8 (&A)[WK<C>::NK][WK<C>::NCT], f32x4 (&acc)[WK<C>::NCT]) {
     constexpr int NK = WK<C>::NK, NCT = WK<C>::NCT, PB = C * 2;
     const int gsel = C == 32 ? g : (g & 1);
@@ -482,7 +485,7 @@ __device__ __forceinline__ void conv_taps_ring(const unsigned char* img, const i
         if (tap > 8) tap = 8;                                    // the weights of the missing tenth tap are zero
         const int kh = tap / 3, kw = tap - 3 * kh;
         const int xc = col + kw * D;
-        const int rb = C == 32 ? ro[k / 3] : (kh == 0 ? ro[0] : (kh == 1 ? ro[1] : ro[2]));
+        const int rb = kh == 0 ? ro0 : (kh == 1 ? ro1 : ro2);
         const e16x8 bq = *reinterpret_cast<const e16x8*>(img + rb + xc * PB + 16 * (gsel ^ rswz<C>(xc)));
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) acc[ct] = mma32(A[k][ct], bq, acc[ct]);
@@ -495,7 +498,8 @@ __device__ __forceinline__ void conv_taps_ring(const unsigned char* img, const i
 // image already in step a., three barriers per step instead of four: 53.18 / 52.62 ms per step against 51.96 / 52.06, profiles/r05_bwds_hd_ab.txt.)
 // SJ (C = 16, with GOUT): the backward of a skip join on this block's input rides on the gated epilogue of step d. (SkipJ, wide_common.h)
 // (The kernel's body is a device function so that the riding form is a kernel of its OWN signature, k_wrb_bwds_sj: one more -- unused --
-// kernel argument on k_wrb_bwds itself moved its register allocation from 127 registers / no spill to 128 / one spilled.)
+// kernel argument on k_wrb_bwds itself moved its register allocation from 127 registers / no spill to 128 / one spilled.  "No spill" was the
+// register report's word: ScratchSize was 16 all along -- see conv_taps_ring; tt_wide_bwd_kernel_attr reads the real figure.)
 template <int C, int D, int TH, int TW, int MINW, bool GOUT, bool SJ>
 __device__ __forceinline__ void wrb_bwds_body(const e16* __restrict__ x, const e16* __restrict__ h1, const e16* __restrict__ dy,
                                               const e16x8* __restrict__ wimg, const float* __restrict__ b2, e16* __restrict__ dx,
@@ -752,33 +756,51 @@ __device__ __forceinline__ void wrb_bwds_body(const e16* __restrict__ x, const e
                 for (int k = 0; k < NK; ++k)
 #pragma unroll
                     for (int ct = 0; ct < NCT; ++ct) A[k][ct] = wp[K::W3 + (k * NCT + ct) * 64 + lane];
+                // A has landed and the compiler knows it: from here on the only requests it counts in this loop are its own dx stores
+#pragma unroll
+                for (int k = 0; k < NK; ++k)
+#pragma unroll
+                    for (int ct = 0; ct < NCT; ++ct) vmem_retired(A[k][ct]);
                 constexpr int GPRW = TW / 16;
-                for (int grp = wave; grp < TH * GPRW; grp += 4) {
-                    const int r = grp / GPRW, c = (grp - r * GPRW) * 16 + n;
-                    const int h = X0 + r;
-                    if (h >= H) break;
-                    const int t = t0 + c;
-                    const bool valid = t < T;
-                    const long pix = ((long)b * H + h) * T + t;
-                    // unconditional (clamped) so that no branch pins a wait in front of the products
-                    const vec_t rq = *reinterpret_cast<const vec_t*>(dy + (valid ? pix : pix - (t - (T - 1))) * C + NCH * g);
-                    vec_t xg, sg0, sg1;
-                    if constexpr (GOUT && XE) xg = *reinterpret_cast<const vec_t*>(xst + (r * TW + c) * PB + 16 * (opiece ^ fswz<C>(c)) + obyte);
-                    else if constexpr (GOUT) xg = *reinterpret_cast<const vec_t*>(x + (valid ? pix : pix - (t - (T - 1))) * C + NCH * g);
-                    if constexpr (SJ) {                          // the join's gradient at this pixel, both batches: requested with dy
-                        const e16* gp = sj.g + (valid ? pix : pix - (t - (T - 1))) * C + NCH * g;
-                        sg0 = *reinterpret_cast<const vec_t*>(gp);
-                        sg1 = *reinterpret_cast<const vec_t*>(gp + sj.half);
-                    }
-                    const int ro[3] = {slot(h - D) * G::ROWB, slot(h) * G::ROWB, slot(h + D) * G::ROWB};
+                static_assert(4 % GPRW == 0, "a wave keeps its column group over the rows of a step");
+                constexpr int RS = 4 / GPRW;
+                // The wave's sixteen columns are the same for every row of the step; a group wholly beside the image has nothing to store and is
+                // not computed, so every group that IS computed issues exactly one dx store (lane 0 of it is inside) -- the counted waits below
+                // rely on that.  Global operands (wide_common.h, gload_ahead): dy always, x in the gated form without its LDS image, the join's
+                // two gradients in the riding form -- the row's base is scalar, the lane's part a 32-bit byte offset clamped into the row.
+                const int c = (wave % GPRW) * 16 + n, t = t0 + c;
+                const bool valid = t < T;
+                const unsigned loff = ((valid ? t : T - 1) * C + NCH * g) * 2;
+                struct Ops { vec_t rq, xg, sg0, sg1; } oa, ob;
+                constexpr bool XG = GOUT && !XE;
+                constexpr int NL = 1 + (XG ? 1 : 0) + (SJ ? 2 : 0);           // requests per group
+                auto request = [&](Ops& o, int hh) {
+                    const long row = ((long)b * H + hh) * T * C;
+                    gload_ahead(o.rq, dy + row, loff);
+                    if constexpr (XG) gload_ahead(o.xg, x + row, loff);
+                    if constexpr (SJ) { gload_ahead(o.sg0, sj.g + row, loff); gload_ahead(o.sg1, sj.g + sj.half + row, loff); }
+                };
+                auto group = [&](Ops& cur, Ops& nxt, int r, int h, bool first) {
+                    // the next group's operands; the step's last group asks for its own row again (inside the tensor, and the count stays the same)
+                    request(nxt, (r + RS < TH && h + RS < H) ? h + RS : h);
+                    if constexpr (GOUT && XE) cur.xg = *reinterpret_cast<const vec_t*>(xst + (r * TW + c) * PB + 16 * (opiece ^ fswz<C>(c)) + obyte);
+                    const int ro0 = slot(h - D) * G::ROWB, ro1 = slot(h) * G::ROWB, ro2 = slot(h + D) * G::ROWB;
                     f32x4 acc[NCT];
 #pragma unroll
                     for (int ct = 0; ct < NCT; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    conv_taps_ring<C, D, GW>(ring, ro, c, g, A, acc);
+                    conv_taps_ring<C, D, GW>(ring, ro0, ro1, ro2, c, g, A, acc);
+                    // younger than this group's operands: the next group's NL requests and -- but for the step's first group -- the previous group's store
+                    if (first) gload_wait<NL>(); else gload_wait<NL + 1>();
+                    gload_use(cur.rq);
+                    if constexpr (XG) gload_use(cur.xg);
+                    if constexpr (SJ) { gload_use(cur.sg0); gload_use(cur.sg1); }
+                    const vec_t rq = cur.rq;
+                    vec_t xg = zero_v;                          // read by the gated forms only
+                    if constexpr (GOUT) xg = cur.xg;
                     vec_t o;
                     if constexpr (SJ) {
                         float add[NCH], dot = 0.f;
-                        skipj_terms<vec_t, NCH>(sg0, sg1, sj.half != 0, xg, sjw, add, dot);
+                        skipj_terms<vec_t, NCH>(cur.sg0, cur.sg1, sj.half != 0, xg, sjw, add, dot);
                         if (valid) sjdot += dot;
 #pragma unroll
                         for (int jj = 0; jj < NCH; ++jj) o[jj] = (e16)((acc[jj >> 2][jj & 3] + (float)rq[jj] + add[jj]) * elu_dout((float)xg[jj]));
@@ -787,7 +809,25 @@ __device__ __forceinline__ void wrb_bwds_body(const e16* __restrict__ x, const e
                         for (int jj = 0; jj < NCH; ++jj)
                             o[jj] = GOUT ? (e16)((acc[jj >> 2][jj & 3] + (float)rq[jj]) * elu_dout((float)xg[jj])) : (e16)(acc[jj >> 2][jj & 3] + (float)rq[jj]);
                     }
-                    if (valid) *reinterpret_cast<vec_t*>(dx + pix * C + NCH * g) = o;
+                    // (loff is the lane's own pixel wherever `valid`; scalar row base + 32-bit offset, as the loads)
+                    if (valid) gstore_counted(o, dx + ((long)b * H + h) * T * C, loff);
+                };
+                int r = wave / GPRW, h = X0 + r;
+                if (t0 + (wave % GPRW) * 16 < T && h < H) {
+                    request(oa, h);
+                    for (bool first = true;; first = false) {                // unrolled by two: the groups in flight alternate between oa and ob
+                        group(oa, ob, r, h, first);
+                        r += RS; h += RS;
+                        if (r >= TH || h >= H) break;
+                        group(ob, oa, r, h, false);
+                        r += RS; h += RS;
+                        if (r >= TH || h >= H) break;
+                    }
+                    // the last group's "next" requests are still on their way into oa / ob: they land before those registers are given to anything else
+                    gload_wait<1>();
+                    gload_use(oa.rq); gload_use(ob.rq);
+                    if constexpr (XG) { gload_use(oa.xg); gload_use(ob.xg); }
+                    if constexpr (SJ) { gload_use(oa.sg0); gload_use(oa.sg1); gload_use(ob.sg0); gload_use(ob.sg1); }
                 }
             }
             if constexpr (!XE) {
@@ -976,6 +1016,27 @@ int ttx_wide_rb_bwd_onepass(LevelCtx* ctx, const void* x, const void* h1, const 
     hipStream_t st = tt_stream(stream);
     if (C == 16) return bwds_c<16>(xi, hi, gi, w1, w2, b2, (e16*)dx, dw1, db1, dw2, db2, (unsigned char*)ws, B, H, T, dilation, st, ctx);
     return bwds_c<32>(xi, hi, gi, w1, w2, b2, (e16*)dx, dw1, db1, dw2, db2, (unsigned char*)ws, B, H, T, dilation, st, ctx);
+}
+
+// the strip kernels launch_bwds chooses from, by (C, dilation, form: 0 plain, 1 gated, 2 riding) -- tt_wide_bwd_kernel_attr (conv_wide_bf16.hip)
+namespace {
+template <int C, int D> int bwds_attr(int form, int* local_bytes, int* num_regs) {
+    constexpr int MINW = C == 32 ? 3 : 4;
+    if (form == 0) return kernel_attr(k_wrb_bwds<C, D, 8, 32, MINW, false>, local_bytes, num_regs);
+    if constexpr (D == 1) {
+        if (form == 1) return kernel_attr(k_wrb_bwds<C, D, 8, 32, MINW, true>, local_bytes, num_regs);
+        if constexpr (C == 16) {
+            if (form == 2) return kernel_attr(k_wrb_bwds_sj<C, D, 8, 32, MINW>, local_bytes, num_regs);
+        }
+    }
+    return TT_E_UNSUPPORTED;
+}
+}  // namespace
+int ttx_wide_bwds_attr(int C, int dilation, int form, int* local_bytes, int* num_regs) {
+#define TT_BA(CC, DD) if (C == CC && dilation == DD) return bwds_attr<CC, DD>(form, local_bytes, num_regs)
+    TT_BA(16, 1); TT_BA(16, 2); TT_BA(16, 3); TT_BA(32, 1); TT_BA(32, 2); TT_BA(32, 3);
+#undef TT_BA
+    return TT_E_UNSUPPORTED;
 }
 
 // called by tt_wide_level_bwd (conv_wide_bf16.hip): the bf16 weight images of n blocks (image i at ws_i, where the one-pass kernels expect

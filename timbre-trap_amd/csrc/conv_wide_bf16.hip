@@ -685,29 +685,46 @@ __global__ __launch_bounds__(NT, (GOUT && C == 32) ? 3 : 2) void k_wrb_dxw(const
         __syncthreads();
 
         // ---- dx = dy + W1^T (*) dA1 over the tile's own pixels ----
+        // The operands from memory -- dy, and the join's two gradients in the riding form -- are requested one pixel group AHEAD and waited for by
+        // count (wide_common.h, gload_ahead; the same loop as step d. of the C = 16 strips, conv_level_bf16.hip).  A wave keeps its sixteen columns
+        // over the rows of the tile; a group wholly beside the image is not computed, so every computed group issues exactly one dx store.
+        // (Round 6 measured "dy one group ahead" as nothing, profiles/r06_pf_ab.txt -- on a build whose prefetch variant spilled four registers at
+        // C = 32, and a spill reload is followed by vmcnt(0) like the load it was meant to hide: that record decided nothing.)
         constexpr int GPRW = TW / 16;
-        for (int grp = wave; grp < TH * GPRW; grp += 4) {
-            const int r = grp / GPRW, c = (grp - r * GPRW) * 16 + n;
+        static_assert(4 % GPRW == 0, "a wave keeps its column group over the rows of a tile");
+        constexpr int RS = 4 / GPRW;
+        const int swave = __builtin_amdgcn_readfirstlane(wave);
+        const int c = (swave % GPRW) * 16 + n, t = t0 + c;
+        const bool valid = t < T;
+        const unsigned loff = ((valid ? t : T - 1) * C + NCH * g) * 2;
+        struct Ops { vec_t rq, sg0, sg1; } oa, ob;
+        constexpr int NL = SJ ? 3 : 1;                               // requests per group
+        // The riding form at C = 32 has three 16-byte operands per lane: two groups of them do not fit the 168 registers (92 bytes of spills, their
+        // reloads in this loop).  It asks for the CURRENT group's operands at the top of the iteration, in front of the products, instead.
+        constexpr bool AHEAD = !(SJ && C == 32);
+        auto request = [&](Ops& o, int hh) {
+            const long row = ((long)b * H + hh) * T * C;
+            gload_ahead(o.rq, dy + row, loff);
+            if constexpr (SJ) { gload_ahead(o.sg0, sj.g + row, loff); gload_ahead(o.sg1, sj.g + sj.half + row, loff); }
+        };
+        auto group = [&](Ops& cur, Ops& nxt, int r, bool first) {
             const int h = h0 + r;
-            if (h >= H) break;
-            const int t = t0 + c;
-            const bool valid = t < T;
-            const long pix = ((long)b * H + h) * T + t;
-            vec_t sg0, sg1;
-            if constexpr (SJ) {                                  // the join's gradient at this pixel, both batches: requested with dy
-                const e16* gp = sj.g + (valid ? pix : pix - (t - (T - 1))) * C + NCH * g;
-                sg0 = *reinterpret_cast<const vec_t*>(gp);
-                sg1 = *reinterpret_cast<const vec_t*>(gp + sj.half);
-            }
-            // unconditional (clamped) so that no branch pins a wait in front of the products.  (Round 6, measured and dropped: dy requested one
-            // pixel group AHEAD of its products, here and in the C = 16 strips' data-gradient phase -- 49.72-49.86 / 49.80-49.86 / 49.85-49.96 ms
-            // per step without / strips only / both, profiles/r06_pf_ab.txt: this latency is already hidden by the CU's other waves.)
-            const vec_t rq = *reinterpret_cast<const vec_t*>(dy + (valid ? pix : pix - (t - (T - 1))) * C + NCH * g);
+            // the next group's operands; the tile's last group asks for its own row again (inside the tensor, and the count stays the same)
+            if constexpr (AHEAD) request(nxt, (r + RS < TH && h + RS < H) ? h + RS : h);
+            else request(cur, h);
             f32x4 acc[NCT];
 #pragma unroll
             for (int ct = 0; ct < NCT; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
             e16x8 unused;
             conv_taps<C, D, G::IW>(gs, r, c, g, A, acc, unused);
+            // younger than this group's operands: the next group's NL requests and -- but for the tile's first group -- the previous group's store
+            // (not AHEAD: this group's operands are the youngest requests)
+            if constexpr (!AHEAD) gload_wait<0>();
+            else if (first) gload_wait<NL>();
+            else gload_wait<NL + 1>();
+            gload_use(cur.rq);
+            if constexpr (SJ) { gload_use(cur.sg0); gload_use(cur.sg1); }
+            const vec_t rq = cur.rq;
             vec_t o;
             if constexpr (GOUT) {
                 // dx * ELU'(x) for the layer in front of the level (see k_nrb_bwd_fused): the lane's channels of x from the halo-free image
@@ -721,7 +738,7 @@ __global__ __launch_bounds__(NT, (GOUT && C == 32) ? 3 : 2) void k_wrb_dxw(const
                                                                  (C == 32 ? 0 : 8 * (g & 1)));
                 if constexpr (SJ) {
                     float add[NCH], dot = 0.f;
-                    skipj_terms<vec_t, NCH>(sg0, sg1, sj.half != 0, xq, sjw, add, dot);
+                    skipj_terms<vec_t, NCH>(cur.sg0, cur.sg1, sj.half != 0, xq, sjw, add, dot);
                     if (valid) sjdot += dot;
 #pragma unroll
                     for (int j = 0; j < NCH; ++j) sum[j] += add[j];
@@ -732,7 +749,27 @@ __global__ __launch_bounds__(NT, (GOUT && C == 32) ? 3 : 2) void k_wrb_dxw(const
 #pragma unroll
                 for (int j = 0; j < NCH; ++j) o[j] = (e16)(acc[j >> 2][j & 3] + (float)rq[j]);
             }
-            if (valid) *reinterpret_cast<vec_t*>(dx + pix * C + NCH * g) = o;
+            if (valid) gstore_counted(o, dx + ((long)b * H + h) * T * C, loff);
+        };
+        int r = swave / GPRW;
+        if (t0 + (swave % GPRW) * 16 < T && h0 + r < H) {
+            if constexpr (AHEAD) {
+                request(oa, h0 + r);
+                for (bool first = true;; first = false) {            // unrolled by two: the groups in flight alternate between oa and ob
+                    group(oa, ob, r, first);
+                    r += RS;
+                    if (r >= TH || h0 + r >= H) break;
+                    group(ob, oa, r, false);
+                    r += RS;
+                    if (r >= TH || h0 + r >= H) break;
+                }
+                // the last group's "next" requests are still on their way into oa / ob: they land before those registers are given to anything else
+                gload_wait<1>();
+                gload_use(oa.rq); gload_use(ob.rq);
+                if constexpr (SJ) { gload_use(oa.sg0); gload_use(oa.sg1); gload_use(ob.sg0); gload_use(ob.sg1); }
+            } else {
+                for (; r < TH && h0 + r < H; r += RS) group(oa, oa, r, false);
+            }
         }
 
         // ---- dW1, K = pixels: 32 consecutive columns of a row per product, both operands by transpose reads ----
@@ -1380,15 +1417,27 @@ __global__ __launch_bounds__(NT, C == 8 ? 2 : TT_NBF2_MINW4) void k_nrb_bwd_fuse
         const int row = q / G::TW, px = q - row * G::TW;
         relx[it] = (unsigned)(row * T + px) * (unsigned)(C * 2);
     }
-    // phase 1, per step s: LDS offset of the lane's pixel (clamped into the image) and key = row | column << 16 of a pixel of the
-    // tile proper, ~0 for a halo pixel: "one of this tile's own in-image pixels" is then (key & 0xffff) < hlim && (key >> 16) < tlim
-    unsigned poff[NS1], pkey[NS1];
+    // phase 1, per step s: key = row | column << 8 of a pixel of the tile proper, 0xffff for a halo pixel: "one of this tile's own in-image
+    // pixels" is then (key & 0xff) < hlim && (key >> 8) < tlim.  Two steps' keys share a register, and the LDS offset of the lane's pixel
+    // (clamped into the image) is two instructions from the lane's first pixel q0: a register per step for each of them (2 NS1 = 10-14) is
+    // what spilled at the 128-register cap of C = 4 -- 7 / 1 / 8 reloads inside the tile loop at dilation 1 / 2 / 3, each followed by
+    // vmcnt(0), which ended the deferred wait for the x tile (point (ii) above) in the middle of phase 1.
+    static_assert(G::ROWS < 255 && G::RW < 255, "row and column of a phase-1 key are bytes");
+    const unsigned q0 = wave * 64 + lane;
+    auto poff_of = [&](unsigned step) -> unsigned { const unsigned q = q0 + step; return (q < (unsigned)NPX ? q : (unsigned)(NPX - 1)) * G::PXB; };
+    auto key_of = [&](int q) -> unsigned {
+        const int qq = q < NPX ? q : NPX - 1;
+        const int row = qq / G::RW, col = qq - row * G::RW;
+        return (q < NPX && row >= D && row < D + G::TH && col >= G::DP && col < G::DP + G::TW) ? (unsigned)row | ((unsigned)col << 8) : 0xffffu;
+    };
+    // The riding form at C = 4 has no registers left for the key table either (its three were the ones reloaded inside phase 1): it works
+    // the key out per step from the step's opaque first pixel -- a division by a constant and four compares per 64 pixels.
+    constexpr bool KEY_PER_STEP = SJ && C == 4;
+    unsigned pkey2[(NS1 + 1) / 2];
 #pragma unroll
     for (int s1 = 0; s1 < NS1; ++s1) {
-        const int q = wave * 64 + s1 * NT + lane, qq = q < NPX ? q : NPX - 1;
-        const int row = qq / G::RW, col = qq - row * G::RW;
-        poff[s1] = (unsigned)qq * G::PXB;
-        pkey[s1] = (q < NPX && row >= D && row < D + G::TH && col >= G::DP && col < G::DP + G::TW) ? (unsigned)row | ((unsigned)col << 16) : 0xffffffffu;
+        const unsigned key = KEY_PER_STEP ? 0u : key_of(wave * 64 + s1 * NT + lane);
+        if (s1 & 1) pkey2[s1 >> 1] |= key << 16; else pkey2[s1 >> 1] = key;
     }
     auto wfrag = [&](int m, int ob, int kb) { return *reinterpret_cast<const s16x4*>(wimg + ((((m * NB + ob) * NB + kb) << 2) + i4) * 8); };
     for (int v = blockIdx.x; v < ntiles; v += gridDim.x) {
@@ -1448,14 +1497,21 @@ __global__ __launch_bounds__(NT, C == 8 ? 2 : TT_NBF2_MINW4) void k_nrb_bwd_fuse
             for (int ob = 0; ob < NB; ++ob)
 #pragma unroll
                 for (int kb = 0; kb < NB; ++kb) { A2[ob][kb] = wfrag(0, ob, kb); A2T[ob][kb] = wfrag(1, ob, kb); }
-            const unsigned hlim = (unsigned)(H - h0 + D), tlim = (unsigned)(T - t0 + G::DP);
+            // (clamped to a byte: 0xff, the halo's key, is then below neither bound; an own pixel's row / column is below 255 anyway)
+            const unsigned hl_ = (unsigned)(H - h0 + D), tl_ = (unsigned)(T - t0 + G::DP);
+            const unsigned hlim = hl_ < 255u ? hl_ : 255u, tlim = tl_ < 255u ? tl_ : 255u;
 #pragma unroll
             for (int s1 = 0; s1 < NS1; ++s1) {
                 const int c0 = wave * 64 + s1 * NT;
                 if (c0 >= NPX) break;
-                const bool centre = (pkey[s1] & 0xffffu) < hlim && (pkey[s1] >> 16) < tlim;
-                const vec_t hq = *reinterpret_cast<const vec_t*>(hs + poff[s1]);
-                const vec_t dq = *reinterpret_cast<const vec_t*>(gs + poff[s1]);
+                // the step's first pixel in a register the compiler cannot see through: what is derived from it is computed HERE, per step, and
+                // not once per kernel for all NS1 steps and kept (that is how the offsets came back as registers, and went to scratch)
+                unsigned step = s1 * NT;
+                asm volatile("" : "+v"(step));
+                const unsigned key = KEY_PER_STEP ? key_of((int)(q0 + step)) : (pkey2[s1 >> 1] >> (16 * (s1 & 1))) & 0xffffu, poff = poff_of(step);
+                const bool centre = (key & 0xffu) < hlim && (key >> 8) < tlim;
+                const vec_t hq = *reinterpret_cast<const vec_t*>(hs + poff);
+                const vec_t dq = *reinterpret_cast<const vec_t*>(gs + poff);
                 f32x4 z[NB], u[NB], gv[NB];
                 e16x4 gq4[NB];
 #pragma unroll
@@ -1490,8 +1546,8 @@ __global__ __launch_bounds__(NT, C == 8 ? 2 : TT_NBF2_MINW4) void k_nrb_bwd_fuse
                 *reinterpret_cast<vec_t*>(abuf + lane * G::PXB) = centre ? gq : zero_px;
                 __builtin_amdgcn_wave_barrier();
                 asm volatile("" ::: "memory");
-                const unsigned char* hb0 = hs + (long)c0 * G::PXB;                   // the 64 pixels of this step, before dA1 replaces them
                 const int so = 32 * (4 * g + trj) + 8 * trq;
+                const unsigned char* hb0 = hs + (wave * 64 + step) * G::PXB;         // the 64 pixels of this step, before dA1 replaces them
                 // transpose reads spelled out: in front of the builtin form the compiler places s_waitcnt vmcnt(0) (an LDS read it cannot
                 // prove disjoint from the x pieces still arriving by LDS-DMA), which is exactly the wait this kernel defers
                 const unsigned ga_ = lds_addr(abuf + so), ha_ = lds_addr(hb0 + so);
@@ -1508,7 +1564,7 @@ __global__ __launch_bounds__(NT, C == 8 ? 2 : TT_NBF2_MINW4) void k_nrb_bwd_fuse
                                  : "=&v"(gt_), "=&v"(ht_) : "v"(ga_), "v"(ha_) : "memory");
                     dw2m = mma16(gt_, ht_, dw2m);
                 }
-                if (c0 + 64 <= NPX || lane < NPX - c0) *reinterpret_cast<vec_t*>(hs + poff[s1]) = aq;
+                if (c0 + 64 <= NPX || lane < NPX - c0) *reinterpret_cast<vec_t*>(hs + poff) = aq;
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // x has had all of phase 1 to arrive
@@ -2028,6 +2084,34 @@ int tt_wide_rb_fwd_join(const void* x, const float* w1, const float* b1, const f
 
 int tt_wide_rb_bwd_is_onepass(int C, int dilation) {
     return (C == 16 || C == 32) && dilation >= 1 && dilation <= 3 ? onepass_choice(C, dilation) : 0;
+}
+
+extern "C++" {
+template <int C, int D> static int dxw_attr(int form, int* local_bytes, int* num_regs) {
+    if (form == 0) return kernel_attr(k_wrb_dxw<C, D, 8, 32, false>, local_bytes, num_regs);
+    if constexpr (D == 1) {
+        if (form == 1) return kernel_attr(k_wrb_dxw<C, D, 8, 32, true>, local_bytes, num_regs);
+        if (form == 2) return kernel_attr(k_wrb_dxw<C, D, 8, 32, true, true>, local_bytes, num_regs);
+    }
+    return TT_E_UNSUPPORTED;
+}
+template <int C, int D> static int nbf_attr(int form, int* local_bytes, int* num_regs) {
+    if (form == 0) return kernel_attr(k_nrb_bwd_fused<C, D, false>, local_bytes, num_regs);
+    if constexpr (D == 1) {
+        if (form == 1) return kernel_attr(k_nrb_bwd_fused<C, D, true>, local_bytes, num_regs);
+        if (form == 2) return kernel_attr(k_nrb_bwd_fused<C, D, true, true>, local_bytes, num_regs);
+    }
+    return TT_E_UNSUPPORTED;
+}
+}  // extern "C++"
+int tt_wide_bwd_kernel_attr(int kernel, int C, int dilation, int form, int* local_bytes, int* num_regs) {
+    if (!local_bytes || !num_regs || form < 0 || form > 2) return TT_E_BADARG;
+    if (kernel == TT_BWD_KERNEL_STRIPS) return ttx_wide_bwds_attr(C, dilation, form, local_bytes, num_regs);
+#define TT_KA(F, CC, DD) if (C == CC && dilation == DD) return F<CC, DD>(form, local_bytes, num_regs)
+    if (kernel == TT_BWD_KERNEL_DXW) { TT_KA(dxw_attr, 16, 1); TT_KA(dxw_attr, 16, 2); TT_KA(dxw_attr, 16, 3); TT_KA(dxw_attr, 32, 1); TT_KA(dxw_attr, 32, 2); TT_KA(dxw_attr, 32, 3); }
+    if (kernel == TT_BWD_KERNEL_NARROW) { TT_KA(nbf_attr, 4, 1); TT_KA(nbf_attr, 4, 2); TT_KA(nbf_attr, 4, 3); TT_KA(nbf_attr, 8, 1); TT_KA(nbf_attr, 8, 2); TT_KA(nbf_attr, 8, 3); }
+#undef TT_KA
+    return TT_E_UNSUPPORTED;
 }
 
 // tt_wide_rb_bwd with the calling level's context (nullptr: the public call)

@@ -49,6 +49,38 @@ __device__ __forceinline__ void conv_taps(const unsigned char* img, int row, int
     }
 }
 
+// ---- global operands requested one pixel group AHEAD of their use (the data-gradient loops) ----------------------------------
+// Left to the compiler, the per-group dy load of those loops is sunk under the `valid` branch behind the matrix products and waited for with
+// vmcnt(0) on the next line -- one request in flight per wave, its whole latency sat out once per group, and the previous group's dx store
+// drained with it.  A load inside an asm statement is neither moved nor counted by the compiler: gload_ahead requests the NEXT group's
+// operand at the top of an iteration (wave-uniform base + 32-bit lane offset, no 64-bit address registers), and gload_wait<N> waits until at
+// most N younger requests are outstanding -- the loop counts its own queue (loads AND its one store per group), and the compiler's own loads
+// must all have retired in front of the loop (vmem_retired), or its waits would count a queue it cannot see and drain ours.
+// The destination is written when the data lands, not at the statement: nothing may read or copy it before gload_wait + gload_use, so the two
+// groups in flight live in two NAMED variables of a loop unrolled by hand (no copy on the back edge).  That pins the ORDER, not the register
+// allocation: "=v" outputs with a separate wait leave the compiler free to copy, spill or reuse a destination while its data is on the way,
+// and a v_mov of a pending register would show only as an intermittent value error that the values tests may or may not catch.  Today's
+// listings are clean; whenever one of these loops, its register pressure or the compiler changes, the listing audit is a REQUIRED step:
+//     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC --cuda-device-only -S <source> -o x.s && python tools/isa_asm_loads.py x.s
+// (no instruction may name an asm load's destination before the counted wait that retires it; bf16 and fp16 sources both).
+// A register spilled INSIDE such a loop would be a request the count does not include (and its reload a vmcnt(0)): the kernels that use this
+// keep ScratchSize 0 or their spills outside the loop -- tt_wide_bwd_kernel_attr, tests/test_gpu_bwd_loops.py, profiles/bwd_loops_isa.txt.
+template <class V> __device__ __forceinline__ void gload_ahead(V& dst, const void* base, unsigned off) {
+    static_assert(sizeof(V) == 8 || sizeof(V) == 16, "a lane's channels of one pixel");
+    if constexpr (sizeof(V) == 8) asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(dst) : "v"(off), "s"(base) : "memory");
+    else asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(off), "s"(base) : "memory");
+}
+// the loop's store in the same addressing, counted with its loads (x3 / x4 stores: a wait state before their data registers may change)
+template <class V> __device__ __forceinline__ void gstore_counted(const V& v, void* base, unsigned off) {
+    static_assert(sizeof(V) == 8 || sizeof(V) == 16, "a lane's channels of one pixel");
+    if constexpr (sizeof(V) == 8) asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(off), "v"(v), "s"(base) : "memory");
+    else asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(off), "v"(v), "s"(base) : "memory");
+}
+template <int N> __device__ __forceinline__ void gload_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+template <class V> __device__ __forceinline__ void gload_use(V& v) { asm volatile("" : "+v"(v)); }     // orders every reader behind the wait
+// every load the compiler issued so far that feeds `v` has retired, and the compiler knows it (it waits in front of a statement that reads v)
+template <class V> __device__ __forceinline__ void vmem_retired(const V& v) { asm volatile("" ::"v"(v)); }
+
 constexpr int MAX_A_WG = 2048, MAX_W_WG = 1024;   // workgroups that leave dumps (bounds the scratch)
 
 // Sum of the register dumps into the fp32 gradients (+=).  1024 threads = REL consecutive dump elements x RSL slices of the
@@ -154,7 +186,18 @@ int ttx_wide_wprep_batch(int C, int n, const float* const* w1, const float* cons
 int ttx_wide_rb_bwd_onepass(LevelCtx* ctx, const void* x, const void* h1, const void* dy, const float* w1, const float* w2, const float* b2,
                             void* dx, float* dw1, float* db1, float* dw2, float* db2, void* ws, int B, int C, int H, int T, int dilation,
                             void* stream);
+// the strip kernels' share of tt_wide_bwd_kernel_attr (they live in conv_level_bf16.hip); not part of the C ABI
+int ttx_wide_bwds_attr(int C, int dilation, int form, int* local_bytes, int* num_regs);
 namespace {
+// what the loaded code object says about one kernel: private (scratch) bytes per lane and registers -- no launch
+template <class Kernel> inline int kernel_attr(Kernel kern, int* local_bytes, int* num_regs) {
+    hipFuncAttributes fa;
+    hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern));
+    if (e != hipSuccess) return (int)e;
+    *local_bytes = (int)fa.localSizeBytes;
+    *num_regs = fa.numRegs;
+    return 0;
+}
 // the per-lane pieces of that epilogue: t[j] = g0[j] + g1[j]; acc += <t, x>; returns w * t[j] through `add`
 template <class V, int N>
 __device__ __forceinline__ void skipj_terms(const V& g0, const V& g1, bool two, const V& xq, float w, float (&add)[N], float& dot) {
