@@ -26,7 +26,6 @@ extern "C" {
 #endif
 
 #define TT_E_BADARG      (-1)
-#define TT_W_JOIN_LEFT 1       /* tt_wide_level_bwd_gated_join only: the level's backward is done, the riding skip join is NOT (see there) */
 #define TT_E_UNSUPPORTED (-2)   /* shape outside the compiled set, or one clip of >= 2^31 elements (32-bit offsets) */
 
 /* flags of tt_resblock_fwd / tt_resblock_bwd: round the operands of the 3x3 convolutions and of dW1 to bf16 for the
@@ -217,7 +216,8 @@ int tt_resblock_bwd(const float* x, const float* h1, const float* dy, const floa
  *   tt_wide_pack    x (B,C,H,T) fp32 planar -> out bf16 [B][H][T][C]          tt_wide_unpack   the inverse   (C = 4..64)
  *   tt_wide_rb_fwd  y = ELU(W2 . ELU(W1 (*)_dil x + b1) + b2) + x ; h1 (may be NULL) = ELU(W1 (*) x + b1) saved for backward
  *   tt_wide_rb_bwd  from x, h1, dy: dx (written), dw1 / db1 / dw2 / db2 (fp32, accumulated +=); ws = tt_wide_scratch_bytes
- *                   bytes of scratch (dL/d(conv1 pre-activation) in bf16, then per-workgroup partial gradients). */
+ *                   bytes of scratch (C = 32: dL/d(conv1 pre-activation) in bf16, then per-workgroup partial gradients; C = 4, 8, 16
+ *                   keep that tensor in LDS and need the partial gradients only -- C = 16: tt_wide_onepass_scratch_bytes). */
 int64_t tt_wide_scratch_bytes(int B, int C, int H, int T);
 int tt_wide_pack(const float* x, void* out, int B, int C, int H, int T, void* stream);
 int tt_wide_unpack(const void* in, float* y, int B, int C, int H, int T, void* stream);
@@ -260,9 +260,10 @@ int tt_wide_level_bwd_gated(int nblocks, const void* const* x, const void* const
  * gated epilogue then writes  dx = (dy + W1^T (*) dA1 + skip_weights[skip_idx] * (g[0] + g[1])) * ELU'(x[0])  -- the embedding's two
  * gradient contributions in one tensor, so that nothing is left to add -- and  skip_dw[skip_idx] += <g[0] + g[1], x[0]>  (times 1 / S under
  * tt_set_loss_scale).  Two more loads per lane and pixel instead of tt_skip_join16_bwd's pass over five tensors.  dilations[0] must be 1
- * (TT_E_UNSUPPORTED before anything is launched otherwise).  Returns TT_W_JOIN_LEFT (> 0) when the level's backward ran but the first
- * block's kernel was one without the riding form (the A/B dispatches TTRAP_DXW=0 / TTRAP_WBWD1 / TTRAP_NARROW_FUSED16=0): the caller then
- * applies the join with tt_skip_join16_bwd(gate | 2) on dx. */
+ * (TT_E_UNSUPPORTED before anything is launched otherwise).  Returns 0 with the level's backward AND the join done: the first block's
+ * kernel has the riding form at every width (C = 4, 8 k_nrb_bwd_fused, C = 16 the strips, C = 32 k_wrb_dxw); never success with the join
+ * left out.  (Version 16 removed the positive return code 1, "level done, join not", with the A/B kernel dispatches -- the
+ * per-stage narrow kernels, the separate data- and weight-gradient kernels, the forced one-pass choice -- that were its only source.) */
 int tt_wide_level_bwd_gated_join(int nblocks, const void* const* x, const void* const* h1, const void* dy, const float* const* w1,
                                  const float* const* w2, const float* const* b2, void* dx, void* tmp0, void* tmp1, float* const* dw1,
                                  float* const* db1, float* const* dw2, float* const* db2, void* ws, int B, int C, int H, int T,
@@ -286,7 +287,7 @@ int tt_wide_rb_bwd_fused(const void* x, const void* dy, const float* w1, const f
  * tt_wide_rb_bwd's per-stage kernels move 7; nothing is recomputed.  Same results as the per-stage kernels: dx bit-identical, the
  * fp32 weight / bias gradients equal up to summation order (modules.py:755-777 differentiated).
  * ws = tt_wide_onepass_scratch_bytes(C) bytes (<= tt_wide_scratch_bytes).  tt_wide_rb_bwd itself takes this path where
- * tt_wide_rb_bwd_is_onepass(C, dilation) says 1 (measured per width / dilation; TTRAP_WBWD1 = 0 / 1 forces a choice). */
+ * tt_wide_rb_bwd_is_onepass(C, dilation) says 1 (measured per width: C = 16). */
 int64_t tt_wide_onepass_scratch_bytes(int C);
 int tt_wide_rb_bwd_onepass(const void* x, const void* h1, const void* dy, const float* w1, const float* w2, const float* b2,
                            void* dx, float* dw1, float* db1, float* dw2, float* db2, void* ws, int B, int C, int H, int T,
@@ -295,7 +296,7 @@ int tt_wide_rb_bwd_is_onepass(int C, int dilation);
 /* What the loaded code object holds for one of the block-backward kernels (version 15; diagnostic, no launch, needs a device):
  * *local_bytes = private (scratch) memory per lane -- stack objects and register spills, 0 for a kernel that keeps everything in
  * registers -- and *num_regs = its vector registers (hipFuncAttributes::localSizeBytes / numRegs).  kernel: TT_BWD_KERNEL_STRIPS
- * (k_wrb_bwds, C = 16 / 32), TT_BWD_KERNEL_DXW (k_wrb_dxw, C = 16 / 32), TT_BWD_KERNEL_NARROW (k_nrb_bwd_fused, C = 4 / 8); dilation
+ * (k_wrb_bwds, C = 16 / 32), TT_BWD_KERNEL_DXW (k_wrb_dxw, C = 32; version 16: no longer compiled at C = 16), TT_BWD_KERNEL_NARROW (k_nrb_bwd_fused, C = 4 / 8); dilation
  * 1..3; form 0 = plain, 1 = gated, 2 = riding (a skip join on the gated epilogue) -- the last two exist at dilation 1 only, the riding
  * strips at C = 16 only.  TT_E_UNSUPPORTED for a combination that is not compiled; > 0: the hipError_t of the attribute query. */
 #define TT_BWD_KERNEL_STRIPS 0

@@ -137,12 +137,11 @@ def _stagewise(C, d, B, H, T):
     dA2r = _r16(dA2)
     dh1 = F.conv2d(dA2r, w2r.transpose(0, 1).contiguous())
     dA1 = dh1 * torch.where(h_k > 0, torch.ones_like(h_k), h_k + 1)
-    fused = os.environ.get('TTRAP_NARROW_FUSED16', '1') != '0'       # round 5: the one-pass kernel at every narrow width and dilation
-    if (C >= 16 and not lib.tt_wide_rb_bwd_is_onepass(C, d)) or (C < 16 and not fused):
+    if C >= 16 and not lib.tt_wide_rb_bwd_is_onepass(C, d):
         da1_k = _planar(ws[:B * H * T * C * 2].view(ELT).view(B, H, T, C))
         _close16(da1_k, dA1, 'dA1')
     else:
-        da1_k = _r16(dA1)          # the fused narrow backward keeps dA1 in LDS: the restatement's own rounded dA1 stands in
+        da1_k = _r16(dA1)          # the narrow backward and the strips keep dA1 in LDS: the restatement's own rounded dA1 stands in
     dx_ref = gr + F.conv_transpose2d(da1_k, w1r, padding=d, dilation=d)
     _close16(_planar(dxb), dx_ref, 'dx')
     # weight gradients from the kernel's own dA1 (fp32 accumulation of exact bf16 products): += semantics on top of 0.5
@@ -1128,19 +1127,8 @@ def test_skip_join_backward_riding_on_the_gated_level_stagewise(C, shape, reps):
             args = (nb, arr(xs[:nb]), arr(hs), ptr(dy), arr([p_[0] for p_ in par]), arr([p_[2] for p_ in par]), arr([p_[3] for p_ in par]), ptr(dx), ptr(t0), ptr(t1),
                     arr([g_[0] for g_ in ga]), arr([g_[1] for g_ in ga]), arr([g_[2] for g_ in ga]), arr([g_[3] for g_ in ga]), ptr(ws), B, C, H, T, dils)
             if ride:
-                rc = lib.tt_wide_level_bwd_gated_join(*args, ptr(sg), reps, ptr(w), 3, ptr(ds), st)
-                # the first block's kernel has a riding form on the default dispatch at every width; the A/B dispatches of
-                # test_separate_kernel_paths_still_agree take kernels without one: the level then says so (TT_W_JOIN_LEFT = 1) and the
-                # caller applies the join, as include/ttrap.h describes
-                if C <= 8:
-                    riding = os.environ.get('TTRAP_NARROW_FUSED16', '1') != '0'
-                elif lib.tt_wide_rb_bwd_is_onepass(C, 1):
-                    riding = C == 16
-                else:
-                    riding = os.environ.get('TTRAP_DXW', '1') != '0'
-                assert rc == (0 if riding else 1), (rc, riding)
-                if rc == 1:
-                    check(lib.tt_skip_join16_bwd(ptr(sg), ptr(xs[0]), ptr(w), 3, ptr(dx), ptr(ds), xs[0].numel(), reps, 3, st), 'join')
+                # the first block's kernel has a riding form at every width: the level and the join are both done
+                assert lib.tt_wide_level_bwd_gated_join(*args, ptr(sg), reps, ptr(w), 3, ptr(ds), st) == 0
             else:
                 check(lib.tt_wide_level_bwd_gated(*args, st), 'level')
                 check(lib.tt_skip_join16_bwd(ptr(sg), ptr(xs[0]), ptr(w), 3, ptr(dx), ptr(ds), xs[0].numel(), reps, 3, st), 'join')
@@ -1240,7 +1228,7 @@ def test_single_block_call_depends_on_its_arguments_only(C, shape):
     for t in [dx0] + g0:
         assert not bool((t == 0.5).all()), 'the call left an output at its fill: the reduce did not run at once'
     rc = lv.call(lv.outputs(), st, join=True)
-    assert rc in (0, 1), rc                                  # 1 = TT_W_JOIN_LEFT: an A/B dispatch without the riding form, the level ran all the same
+    assert rc == 0, rc
     torch.cuda.synchronize()
     dx1, g1 = single()
     assert lv.call(lv.outputs(), st, join=True, dil=(2, 2, 3)) < 0      # a first block at another dilation: refused
@@ -1312,16 +1300,6 @@ def _pytest_subprocess(env_extra, selection):
                        capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
     return r.stdout
-
-
-@pytest.mark.slow          # the entry points of this opt-in / A-B path run stage-wise in the default selection (test_wide_block_stagewise, tests/test_gpu_determinism.py)
-@pytest.mark.skipif(os.environ.get('TT_CHILD_PYTEST') == '1', reason='already inside the child run')
-def test_separate_kernel_paths_still_agree():
-    """TTRAP_DXW=0 / TTRAP_NDXW=0 / TTRAP_W4X=0: data gradient and weight gradient as separate kernels (the round-2 structure, kept
-    for A/B) against the same stage-wise restatement."""
-    out = _pytest_subprocess(dict(TTRAP_DXW='0', TTRAP_NDXW='0', TTRAP_W4X='0', TTRAP_NARROW_FUSED16='0', TT_CHILD_PYTEST='1'),
-                             ['tests/test_gpu_wide_bf16.py', '-k', 'stagewise and (shape0 or shape3) or strided or sconv or tconv'])
-    assert ' passed' in out
 
 
 @pytest.mark.slow          # the entry points of this opt-in / A-B path run stage-wise in the default selection (test_wide_block_stagewise, tests/test_gpu_determinism.py)

@@ -954,7 +954,7 @@ int launch_bwds(const e16* x, const e16* h1, const e16* dy, const float* w1, con
     static const int per_cu = tt_tune("TTRAP_BWDS_PER_CU", MINW);
     int grid = grid_for(nstrips, G::LDS_BYTES, per_cu);
     if (grid > MAX_W_WG) grid = MAX_W_WG;
-    const FirstForm form = first_form(ctx, D, C == 16);          // a level's first block: dx leaves gated; the riding form exists at C = 16 only
+    const FirstForm form = first_form(ctx, D);                   // a level's first block: dx leaves gated; the riding form exists at C = 16 only
     if constexpr (D == 1) {
         if (form == FirstForm::Riding) {
             if constexpr (C == 16) {
@@ -962,6 +962,8 @@ int launch_bwds(const e16* x, const e16* h1, const e16* dy, const float* w1, con
                 auto kj = k_wrb_bwds_sj<C, D, TH, TW, MINW>;
                 if (int rc = raise_lds(kj, G::LDS_BYTES, once_j)) return rc;
                 hipLaunchKernelGGL(kj, dim3(grid), dim3(NT), G::LDS_BYTES, st, x, h1, dy, wimg, b2, dx, part_a, part_w, B, H, T, tiles_t, nstrips, ctx->skip);
+            } else {
+                return TT_E_UNSUPPORTED;                         // never success with the join dropped (no level sends C = 32 here)
             }
         } else if (form == FirstForm::Gated) {
             static AttrOnce once_g;

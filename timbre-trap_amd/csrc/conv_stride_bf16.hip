@@ -4,11 +4,11 @@
 //   DecoderBlock.tconv   y[h,t,c]   = ELU(b[c]  + sum_{ci<2C, kh = h (mod 2)} W[ci][c][kh] x[(h-kh)/2,t,ci])   2C -> C, H -> 2H+2+p
 // Both weights are (2C, C, 4, 1) tensors; with index(wide, narrow, kh) = (wide * C + narrow) * 4 + kh they are the SAME
 // array layout, and the four products of the two layers are two kernels:
-//   k_s4  "gather four rows"   out[ho] <- in rows 2ho..2ho+3, C -> 2C channels:  sconv forward, tconv data gradient
-//   k_p2  "two rows by parity" out[h]  <- in rows (h - kh)/2,  2C -> C channels:  tconv forward, sconv data gradient
-// Everything is pointwise along T, so the B operand of v_mfma_f32_16x16x32_bf16 (one lane = one pixel, eight channels)
-// comes straight from HBM as 16-byte loads -- no LDS, no halo.  In the data-gradient use the operand is gated on the fly,
-// g = dy * ELU'(y) from the saved OUTPUT y, so no separate gating pass and no scratch tensor.
+//   k_s4  "gather four rows"   out[ho] <- in rows 2ho..2ho+3, C -> 2C channels:  sconv forward
+//   k_p2  "two rows by parity" out[h]  <- in rows (h - kh)/2,  2C -> C channels:  tconv forward, sconv data gradient at C = 32
+// (every other data gradient rides in k_w4's pass).  Everything is pointwise along T, so the B operand of v_mfma_f32_16x16x32_bf16
+// (one lane = one pixel, eight channels) comes straight from HBM as 16-byte loads -- no LDS, no halo.  In the data-gradient use the
+// operand is gated on the fly, g = dy * ELU'(y) from the saved OUTPUT y, so no separate gating pass and no scratch tensor.
 //   k_w4  weight gradient  dW[a][b][kh] = sum small[r,t,a] * big[2r+kh,t,b]  (+ the bias gradient = sum of the gated
 //         operand): K = pixels; both operands from channel-innermost LDS images by transpose reads (ds_read_b64_tr_b16),
 //         the gated one staged through registers, the other by LDS-DMA.  Per-wave register dumps, summed by k_w4_reduce.
@@ -92,8 +92,9 @@ __device__ __forceinline__ void store_lane(e16* out, long pix, int g, const floa
 // two sets of six 16-byte pieces (and their gates) put the kernel at 240-276 registers = one or two waves per SIMD; without the second
 // set it is 160-208 and the waves cover each other instead (round 3, library A/B: tconv C = 32 forward 0.145 -> 0.120 ms, backward
 // 0.520 -> 0.487 ms, sconv backward 0.456 -> 0.426 ms).
-template <int C, bool GATE, bool ACT>
-__global__ __launch_bounds__(NT) void k_s4(const e16* __restrict__ in, const e16* __restrict__ gy,
+// (the second argument is k_p2's saved output for the gate: not read here -- the four kernels of this family keep one argument block)
+template <int C, bool ACT>
+__global__ __launch_bounds__(NT) void k_s4(const e16* __restrict__ in, const e16* __restrict__,
                                             const float* __restrict__ w, const float* __restrict__ bias,
                                             e16* __restrict__ out, int B, int Hin, int Hout, int T, int tb, long ngroups) {
     using S = S4<C>;
@@ -115,7 +116,7 @@ __global__ __launch_bounds__(NT) void k_s4(const e16* __restrict__ in, const e16
     for (int e = 0; e < NCH; ++e) br[e] = (ACT && NCH * g + e < COUT) ? bias[NCH * g + e] : 0.f;
 
     // C >= 16: one group = 16 frames of the output-row PAIR 2m, 2m + 1, which share two of their four input rows: six rows are
-    // fetched (and, in the data-gradient use, gated) for two outputs instead of eight.  Pieces: one row each at C = 32, the two rows
+    // fetched for two outputs instead of eight.  Pieces: one row each at C = 32, the two rows
     // of a tap pair at C = 16; output o uses pieces o * OFS + j.  C <= 8 (all four rows in one piece): one output row per group.
     constexpr bool PAIR = C >= 16;
     constexpr int NO = PAIR ? 2 : 1, OFS = PAIR ? S::NS / 2 : 0, NPC = S::NS + OFS;
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(NT) void k_s4(const e16* __restrict__ in, const e16
         for (int j = 0; j < NPC; ++j) {
             // piece j of output 0 is step j; beyond NS it is step (j - OFS) of output 1
             const int hi = 2 * (NO * m) + (j < S::NS ? S::kh(j, g) : 2 + S::kh(j - OFS, g));
-            q[j] = load_gated<S::CE>(in, gy, (((long)b * Hin + hi) * T + t) * C + S::c0(g), grp < (int)ngroups && t < T && hi < Hin, GATE);
+            q[j] = load_gated<S::CE>(in, nullptr, (((long)b * Hin + hi) * T + t) * C + S::c0(g), grp < (int)ngroups && t < T && hi < Hin, false);
         }
     };
     const int gstride = gridDim.x * 4;                            // ngroups < 2^31 (checked by the launcher): 32-bit scalar arithmetic
@@ -265,15 +266,15 @@ __global__ __launch_bounds__(NT) void k_p2(const e16* __restrict__ in, const e16
 __device__ __forceinline__ s16x4 lo4(e16x8 v) { return __builtin_bit_cast(s16x4, __builtin_shufflevector(v, v, 0, 1, 2, 3)); }
 __device__ __forceinline__ s16x4 hi4(e16x8 v) { return __builtin_bit_cast(s16x4, __builtin_shufflevector(v, v, 4, 5, 6, 7)); }
 
-// all N channels of one pixel as N / 4 four-channel operands of the 4x4x4 product, optionally gated by the saved output
-template <int N, bool GATE>
-__device__ __forceinline__ void load_px(const e16* in, const e16* gy, long off, bool ok, s16x4 (&c)[N / 4]) {
+// all N channels of one pixel as N / 4 four-channel operands of the 4x4x4 product
+template <int N>
+__device__ __forceinline__ void load_px(const e16* in, long off, bool ok, s16x4 (&c)[N / 4]) {
     if constexpr (N == 4) {
-        c[0] = __builtin_bit_cast(s16x4, load_gated<4>(in, gy, off, ok, GATE));
+        c[0] = __builtin_bit_cast(s16x4, load_gated<4>(in, nullptr, off, ok, false));
     } else {
 #pragma unroll
         for (int q = 0; q < N / 8; ++q) {
-            const e16x8 v = load_gated<8>(in, gy, off + 8 * q, ok, GATE);
+            const e16x8 v = load_gated<8>(in, nullptr, off + 8 * q, ok, false);
             c[2 * q] = lo4(v); c[2 * q + 1] = hi4(v);
         }
     }
@@ -298,8 +299,8 @@ __device__ __forceinline__ void store_px(e16* out, long off, const f32x4 (&acc)[
 }
 
 // "gather four rows", C -> 2C (C = 4, 8); one group = 64 frames of the output-row pair 2m, 2m + 1: six input rows for two outputs
-template <int C, bool GATE, bool ACT>
-__global__ __launch_bounds__(NT) void k_s4n(const e16* __restrict__ in, const e16* __restrict__ gy,
+template <int C, bool ACT>
+__global__ __launch_bounds__(NT) void k_s4n(const e16* __restrict__ in, const e16* __restrict__,
                                              const float* __restrict__ w, const float* __restrict__ bias,
                                              e16* __restrict__ out, int B, int Hin, int Hout, int T, int tb, long ngroups) {
     constexpr int NBI = C / 4, NBO = C / 2, CO = 2 * C;
@@ -328,7 +329,7 @@ __global__ __launch_bounds__(NT) void k_s4n(const e16* __restrict__ in, const e1
 #pragma unroll
         for (int r = 0; r < 6; ++r) {
             const int hi = 4 * m + r;
-            load_px<C, GATE>(in, gy, (((long)b * Hin + hi) * T + t) * C, grp < (int)ngroups && t < T && hi < Hin, q[r]);
+            load_px<C>(in, (((long)b * Hin + hi) * T + t) * C, grp < (int)ngroups && t < T && hi < Hin, q[r]);
         }
     };
     // Neighbouring row pairs share two of their six input rows.  Workgroups go to the XCDs round-robin, each XCD has its own L2, and in
@@ -368,8 +369,8 @@ __global__ __launch_bounds__(NT) void k_s4n(const e16* __restrict__ in, const e1
 }
 
 // "two rows by parity", 2C -> C (C = 4, 8); one group = 64 frames of the output-row pair 2m, 2m + 1 from input rows m, m - 1
-template <int C, bool GATE, bool ACT>
-__global__ __launch_bounds__(NT) void k_p2n(const e16* __restrict__ in, const e16* __restrict__ gy,
+template <int C, bool ACT>
+__global__ __launch_bounds__(NT) void k_p2n(const e16* __restrict__ in, const e16* __restrict__,
                                              const float* __restrict__ w, const float* __restrict__ bias,
                                              e16* __restrict__ out, int B, int Hin, int Hout, int T, int tb, long ngroups) {
     constexpr int CI = 2 * C, NBI = CI / 4, NBO = C / 4;
@@ -400,7 +401,7 @@ __global__ __launch_bounds__(NT) void k_p2n(const e16* __restrict__ in, const e1
 #pragma unroll
         for (int rs = 0; rs < 2; ++rs) {
             const int hi = m - rs;
-            load_px<CI, GATE>(in, gy, (((long)b * Hin + hi) * T + t) * CI, grp < (int)ngroups && t < T && hi >= 0 && hi < Hin, q[rs]);
+            load_px<CI>(in, (((long)b * Hin + hi) * T + t) * CI, grp < (int)ngroups && t < T && hi >= 0 && hi < Hin, q[rs]);
         }
     };
     const int nvb = ((int)ngroups + 3) >> 2;                      // XCD-contiguous group order: see k_s4n (each input row serves two groups)
@@ -897,21 +898,21 @@ inline int flat_grid(long ngroups) {
     return (int)(want < cap ? want : cap);
 }
 
-template <int C, bool GATE, bool ACT>
-int launch_s4(const e16* in, const e16* gy, const float* w, const float* bias, e16* out, int B, int Hin, int Hout, int T,
-              hipStream_t st) {
-    if constexpr (C == 4 || (C == 8 && !GATE)) {              // gated C = 8 (tconv data gradient): the 16-row tile form is faster (0.21 vs 0.26 ms)
+template <int C, bool ACT>
+int launch_s4(const e16* in, const float* w, const float* bias, e16* out, int B, int Hin, int Hout, int T, hipStream_t st) {
+    const e16* gy = nullptr;                                     // no gate in this family's C -> 2C kernels (see k_s4)
+    if constexpr (C <= 8) {
         const int tb = (T + 63) / 64;
         const long ngroups = (long)B * ((Hout + 1) / 2) * tb;
         if (ngroups >= (1l << 30)) return TT_E_UNSUPPORTED;       // 32-bit group indices in the kernels
-        hipLaunchKernelGGL((k_s4n<C, GATE, ACT>), dim3(flat_grid(ngroups)), dim3(NT), 0, st, in, gy, w, bias, out, B, Hin, Hout, T, tb, ngroups);
+        hipLaunchKernelGGL((k_s4n<C, ACT>), dim3(flat_grid(ngroups)), dim3(NT), 0, st, in, gy, w, bias, out, B, Hin, Hout, T, tb, ngroups);
         TT_LAUNCH_CHECK();
         return 0;
     }
     const int tb = (T + 15) / 16;
     const long ngroups = (long)B * (C >= 16 ? (Hout + 1) / 2 : Hout) * tb;       // C >= 16: pairs of output rows
     if (ngroups >= (1l << 30)) return TT_E_UNSUPPORTED;
-    hipLaunchKernelGGL((k_s4<C, GATE, ACT>), dim3(flat_grid(ngroups)), dim3(NT), 0, st, in, gy, w, bias, out, B, Hin, Hout, T, tb, ngroups);
+    hipLaunchKernelGGL((k_s4<C, ACT>), dim3(flat_grid(ngroups)), dim3(NT), 0, st, in, gy, w, bias, out, B, Hin, Hout, T, tb, ngroups);
     TT_LAUNCH_CHECK();
     return 0;
 }
@@ -919,10 +920,11 @@ template <int C, bool GATE, bool ACT>
 int launch_p2(const e16* in, const e16* gy, const float* w, const float* bias, e16* out, int B, int Hin, int Hout, int T,
               hipStream_t st) {
     if constexpr (C <= 8) {
+        static_assert(!GATE, "the gated 2C -> C product (a strided layer's data gradient) is a kernel of its own at C = 32 only");
         const int tb = (T + 63) / 64;
         const long ngroups = (long)B * ((Hout + 1) / 2) * tb;
         if (ngroups >= (1l << 30)) return TT_E_UNSUPPORTED;       // 32-bit group indices in the kernels
-        hipLaunchKernelGGL((k_p2n<C, GATE, ACT>), dim3(flat_grid(ngroups)), dim3(NT), 0, st, in, gy, w, bias, out, B, Hin, Hout, T, tb, ngroups);
+        hipLaunchKernelGGL((k_p2n<C, ACT>), dim3(flat_grid(ngroups)), dim3(NT), 0, st, in, gy, w, bias, out, B, Hin, Hout, T, tb, ngroups);
         TT_LAUNCH_CHECK();
         return 0;
     }
@@ -933,12 +935,6 @@ int launch_p2(const e16* in, const e16* gy, const float* w, const float* bias, e
     TT_LAUNCH_CHECK();
     return 0;
 }
-// the data gradient rides along in the weight-gradient pass where the registers allow it (TTRAP_W4X=0: always two kernels)
-template <int C> inline bool w4x_enabled() {
-    static const int on = tt_switch("TTRAP_W4X", 1);
-    return on && C <= 32;
-}
-
 template <int C, bool GS, bool DX, bool PRE = false, bool GDX = false>
 int launch_w4(const e16* small, const e16* big, const e16* ygate, float* dw, float* db, float* ws, const float* w, e16* dx,
               int B, int Hs, int Hb, int T, hipStream_t st) {
@@ -993,7 +989,7 @@ int tt_sconv16_fwd(const void* x, const float* w, const float* b, void* y, int B
     if (!x || !w || !b || !y || !ok_shape(B, C, H, T)) return TT_E_BADARG;
     const int Ho = (H - 4) / 2 + 1;
     hipStream_t st = tt_stream(stream);
-    TT_BY_C(C, (launch_s4<CC, false, true>((const e16*)x, nullptr, w, b, (e16*)y, B, H, Ho, T, st)));
+    TT_BY_C(C, (launch_s4<CC, true>((const e16*)x, w, b, (e16*)y, B, H, Ho, T, st)));
 }
 
 int tt_sconv16_bwd(const void* x, const void* y, const void* dy, const float* w, void* dx, float* dw, float* db, void* ws, int B,
@@ -1001,22 +997,15 @@ int tt_sconv16_bwd(const void* x, const void* y, const void* dy, const float* w,
     if (!x || !y || !dy || !w || !dw || !db || !ws || !ok_shape(B, C, H, T)) return TT_E_BADARG;
     const int Ho = (H - 4) / 2 + 1;
     hipStream_t st = tt_stream(stream);
-    if (dx && C <= 16 && w4x_enabled<32>()) {                     // one pass: weight, bias and data gradient
-        switch (C) {      // C = 32: the gated-small form spills with the data-gradient weights aboard (0.512 vs 0.400 ms in two kernels) -- not merged
+    // the data gradient rides along in the weight-gradient pass where the registers allow it: one pass for weight, bias and data gradient
+    if (dx && C == 32) {  // C = 32: the gated-small form spills with the data-gradient weights aboard (0.512 vs 0.400 ms in two kernels) -- not merged
+        if (int rc = launch_p2<32, true, false>((const e16*)dy, (const e16*)y, w, nullptr, (e16*)dx, B, Ho, H, T, st)) return rc;
+    } else if (dx) {
+        switch (C) {
             case 4: return launch_w4<4, true, true>((const e16*)dy, (const e16*)x, (const e16*)y, dw, db, (float*)ws, w, (e16*)dx, B, Ho, H, T, st);
             case 8: return launch_w4<8, true, true>((const e16*)dy, (const e16*)x, (const e16*)y, dw, db, (float*)ws, w, (e16*)dx, B, Ho, H, T, st);
             case 16: return launch_w4<16, true, true>((const e16*)dy, (const e16*)x, (const e16*)y, dw, db, (float*)ws, w, (e16*)dx, B, Ho, H, T, st);
         }
-    }
-    if (dx) {
-        int rc = TT_E_UNSUPPORTED;
-        switch (C) {
-            case 4: rc = launch_p2<4, true, false>((const e16*)dy, (const e16*)y, w, nullptr, (e16*)dx, B, Ho, H, T, st); break;
-            case 8: rc = launch_p2<8, true, false>((const e16*)dy, (const e16*)y, w, nullptr, (e16*)dx, B, Ho, H, T, st); break;
-            case 16: rc = launch_p2<16, true, false>((const e16*)dy, (const e16*)y, w, nullptr, (e16*)dx, B, Ho, H, T, st); break;
-            case 32: rc = launch_p2<32, true, false>((const e16*)dy, (const e16*)y, w, nullptr, (e16*)dx, B, Ho, H, T, st); break;
-        }
-        if (rc) return rc;
     }
     TT_BY_C(C, (launch_w4<CC, true, false>((const e16*)dy, (const e16*)x, (const e16*)y, dw, db, (float*)ws, nullptr, nullptr, B, Ho, H, T, st)));
 }
@@ -1035,24 +1024,8 @@ int tt_tconv16_bwd(const void* x, const void* y, const void* dy, const float* w,
     const int Ho = 2 * H + 2 + out_pad;
     if (!ok_shape(B, C, Ho, T)) return TT_E_BADARG;
     hipStream_t st = tt_stream(stream);
-    if (dx && w4x_enabled<32>()) {
-        switch (C) {
-            case 32: return launch_w4<32, false, true>((const e16*)x, (const e16*)dy, (const e16*)y, dw, db, (float*)ws, w, (e16*)dx, B, H, Ho, T, st);
-            case 4: return launch_w4<4, false, true>((const e16*)x, (const e16*)dy, (const e16*)y, dw, db, (float*)ws, w, (e16*)dx, B, H, Ho, T, st);
-            case 8: return launch_w4<8, false, true>((const e16*)x, (const e16*)dy, (const e16*)y, dw, db, (float*)ws, w, (e16*)dx, B, H, Ho, T, st);
-            case 16: return launch_w4<16, false, true>((const e16*)x, (const e16*)dy, (const e16*)y, dw, db, (float*)ws, w, (e16*)dx, B, H, Ho, T, st);
-        }
-    }
-    if (dx) {
-        int rc = TT_E_UNSUPPORTED;
-        switch (C) {
-            case 4: rc = launch_s4<4, true, false>((const e16*)dy, (const e16*)y, w, nullptr, (e16*)dx, B, Ho, H, T, st); break;
-            case 8: rc = launch_s4<8, true, false>((const e16*)dy, (const e16*)y, w, nullptr, (e16*)dx, B, Ho, H, T, st); break;
-            case 16: rc = launch_s4<16, true, false>((const e16*)dy, (const e16*)y, w, nullptr, (e16*)dx, B, Ho, H, T, st); break;
-            case 32: rc = launch_s4<32, true, false>((const e16*)dy, (const e16*)y, w, nullptr, (e16*)dx, B, Ho, H, T, st); break;
-        }
-        if (rc) return rc;
-    }
+    // with dx: weight, bias and data gradient in one pass at every width
+    if (dx) { TT_BY_C(C, (launch_w4<CC, false, true>((const e16*)x, (const e16*)dy, (const e16*)y, dw, db, (float*)ws, w, (e16*)dx, B, H, Ho, T, st))); }
     TT_BY_C(C, (launch_w4<CC, false, false>((const e16*)x, (const e16*)dy, (const e16*)y, dw, db, (float*)ws, nullptr, nullptr, B, H, Ho, T, st)));
 }
 

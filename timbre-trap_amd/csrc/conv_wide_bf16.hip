@@ -15,12 +15,12 @@
 //
 // Kernels (all persistent, XCD-ordered tile walk):
 //   k_wide_pack / k_wide_unpack    fp32 planar <-> bf16 channel-innermost at the two ends of a level
-//   k_wrb_conv<C,D,0>              y = ELU(W2 . ELU(W1 (*)_D x + b1) + b2) + x, optionally saving h1 = ELU(W1 (*) x + b1)
-//   k_wrb_conv<C,D,1>              dx = dy + W1^T (*)_D dA1   (same main loop, weights transposed and taps reversed)
+//   k_wrb_conv<C,D,0 / 2>          y = ELU(W2 . ELU(W1 (*)_D x + b1) + b2) + x, optionally saving h1 = ELU(W1 (*) x + b1); 2: with a weighted
+//                                  skip join added in the epilogue
 //   k_wrb_bwd_a<C>                 pointwise chain of the backward: a2 = W2 h1 + b2, dA2 = dy ELU'(a2), dh1 = W2^T dA2,
 //                                  dA1 = dh1 ELU'(a1); dW2, db1, db2 partials
-//   k_wrb_wgrad<C,D>               dW1[co][ci][tap] = sum_pix dA1[co][pix] x[ci][pix + tap]: K = pixels, both operands by
-//                                  LDS transpose reads (ds_read_b64_tr_b16) from channel-innermost images
+//   k_wrb_dxw<C,D>                 dx = dy + W1^T (*)_D dA1 and dW1[co][ci][tap] = sum_pix dA1[co][pix] x[ci][pix + tap] from one staging of
+//                                  dA1: B-operand reads for dx, K = pixels with both operands by LDS transpose reads (ds_read_b64_tr_b16) for dW1
 //   k_wrb_reduce<C>                sums the per-wave register dumps into the fp32 gradients (+=) in a fixed order: no atomics (the
 //                                  narrow levels' k_nrb_reduce below also adds the 16 / C diagonal contributions of a dW1 element in a
 //                                  fixed order: bit-identical from run to run, tests/test_gpu_determinism.py)
@@ -107,10 +107,10 @@ template <int C, int D> struct WT {
     static constexpr int LDS_BYTES = NPR * 16;
 };
 
-// MODE 0: x -> y (and h1 if SAVE).  MODE 1: x = dA1, res = dy, y = dx; b1 / w2 / b2 unused.
+// MODE 0: x -> y (and h1 if SAVE).
 // MODE 2 (round 6): MODE 0 with a weighted skip join in the epilogue -- y = block(x) + jw[0] * res[b mod jB], res = an encoder embedding of
 // jB clips (reference modules.py:112, :569-589: the join behind a DecoderBlock; b mod jB: both halves of a pair decode take the same
-// embedding).  One more 16- / 8-byte load per lane, requested before the products like MODE 1's dy; one rounding of the joined value.
+// embedding).  One more 16- / 8-byte load per lane, requested before the products; one rounding of the joined value.
 // MINW = waves per SIMD the register allocation must allow: at C = 32 the forward holds 72 + 8 VGPRs of weights and lands
 // at 172-176 registers -- two workgroups per CU -- unless capped at 168 (MINW = 3: four registers spill to scratch).
 template <int C, int D, int MODE, bool SAVE, int MINW>
@@ -120,7 +120,8 @@ __global__ __launch_bounds__(NT, MINW) void k_wrb_conv(const e16* __restrict__ x
                                                  e16* __restrict__ y, e16* __restrict__ h1, int B, int H, int T,
                                                  int tiles_h, int tiles_t, int ntiles, const float* __restrict__ jw, int jB) {
     using G = WT<C, D>;
-    constexpr bool FWD = MODE != 1, JOIN = MODE == 2;
+    static_assert(MODE == 0 || MODE == 2, "the block forward, plain or with a skip join");
+    constexpr bool JOIN = MODE == 2;
     float jsc = 0.f;
     if constexpr (JOIN) jsc = jw ? jw[0] : 1.f;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -145,9 +146,9 @@ __global__ __launch_bounds__(NT, MINW) void k_wrb_conv(const e16* __restrict__ x
                 else { tap = 2 * k + (g >> 1); kc = 8 * (g & 1) + j; }
                 const int mo = chan_of<C>(ct, n);                // output channel of row n
                 float wv = 0.f;
-                if (tap < 9) wv = FWD ? w1[(mo * C + kc) * 9 + tap] : w1[(kc * C + mo) * 9 + (8 - tap)];
+                if (tap < 9) wv = w1[(mo * C + kc) * 9 + tap];
                 v[j] = wv;
-                if (FWD) chk = poison_acc(chk, wv);
+                chk = poison_acc(chk, wv);
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) A[k][ct][j] = (e16)v[j];
@@ -155,28 +156,26 @@ __global__ __launch_bounds__(NT, MINW) void k_wrb_conv(const e16* __restrict__ x
     e16x8 A2[NCT];                                              // C = 32: W2 rows (K = 32)
     s16x4 A2s;                                                   // C = 16: W2 rows (K = 16)
     float b1r[NCH], b2r[NCH];
-    if constexpr (FWD) {
-        if constexpr (C == 32) {
+    if constexpr (C == 32) {
 #pragma unroll
-            for (int ct = 0; ct < NCT; ++ct)
+        for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float wv = w2[chan_of<C>(ct, n) * C + 8 * g + j];
-                    chk = poison_acc(chk, wv);
-                    A2[ct][j] = (e16)wv;
-                }
-        } else {
-            e16x4 t;
+            for (int j = 0; j < 8; ++j) {
+                const float wv = w2[chan_of<C>(ct, n) * C + 8 * g + j];
+                chk = poison_acc(chk, wv);
+                A2[ct][j] = (e16)wv;
+            }
+    } else {
+        e16x4 t;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { const float wv = w2[n * C + 4 * g + j]; chk = poison_acc(chk, wv); t[j] = (e16)wv; }
-            A2s = __builtin_bit_cast(s16x4, t);
-        }
-#pragma unroll
-        for (int j = 0; j < NCH; ++j) { b1r[j] = b1[NCH * g + j]; b2r[j] = b2[NCH * g + j]; chk = poison_acc(poison_acc(chk, b1r[j]), b2r[j]); }
+        for (int j = 0; j < 4; ++j) { const float wv = w2[n * C + 4 * g + j]; chk = poison_acc(chk, wv); t[j] = (e16)wv; }
+        A2s = __builtin_bit_cast(s16x4, t);
     }
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) { b1r[j] = b1[NCH * g + j]; b2r[j] = b2[NCH * g + j]; chk = poison_acc(poison_acc(chk, b1r[j]), b2r[j]); }
     // a NaN / inf weight or bias must reach the output like in torch (the ELU forms below return 0 for a NaN pre-activation): the
     // workgroup then writes NaN to every output it owns
-    const bool poisoned = FWD && params_poisoned(chk);          // (a non-finite join weight propagates through the fma by itself)
+    const bool poisoned = params_poisoned(chk);                 // (a non-finite join weight propagates through the fma by itself)
 
     const e16* zero = reinterpret_cast<const e16*>(&g_wzero16);
     for (int v = blockIdx.x; v < ntiles; v += gridDim.x) {
@@ -231,13 +230,8 @@ __global__ __launch_bounds__(NT, MINW) void k_wrb_conv(const e16* __restrict__ x
             }
             f32x4 acc[NCT];                                      // the bias enters as the accumulator's initial value
 #pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) {
-                if constexpr (FWD) acc[ct] = f32x4{b1r[4 * ct], b1r[4 * ct + 1], b1r[4 * ct + 2], b1r[4 * ct + 3]};
-                else acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-            typename std::conditional<C == 32, e16x8, e16x4>::type rq;      // MODE 1: dy of this pixel, requested early
-            if constexpr (MODE == 1)            // unconditional (clamped) so that no branch pins a wait in front of the products
-                rq = *reinterpret_cast<const decltype(rq)*>(res + (valid ? pix : pix - (t - (T - 1))) * C + NCH * g);
+            for (int ct = 0; ct < NCT; ++ct) acc[ct] = f32x4{b1r[4 * ct], b1r[4 * ct + 1], b1r[4 * ct + 2], b1r[4 * ct + 3]};
+            typename std::conditional<C == 32, e16x8, e16x4>::type rq;
             if constexpr (JOIN) {               // the embedding's pixel of clip b mod jB: this row's arrived a row ago, the next row's goes out
                 rq = jq;
                 const int hn = h + 1 < H ? h + 1 : H - 1;
@@ -264,55 +258,39 @@ __global__ __launch_bounds__(NT, MINW) void k_wrb_conv(const e16* __restrict__ x
 #pragma unroll
                 for (int j = 0; j < 4; ++j) val[j] = acc[0][j];
             }
-            if constexpr (MODE == 1) {
-                if (valid) {
-                    if constexpr (C == 32) {
-                        e16x8 o;
 #pragma unroll
-                        for (int j = 0; j < 8; ++j) o[j] = (e16)(val[j] + (float)rq[j]);
-                        *reinterpret_cast<e16x8*>(y + pix * C + 8 * g) = o;
+            for (int j = 0; j < NCH; ++j) val[j] = elu_res(val[j]);
+            if constexpr (C == 32) {
+                e16x8 hq;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) hq[j] = (e16)val[j];
+                if (SAVE && valid) h1_store(reinterpret_cast<e16x8*>(h1 + pix * C + 8 * g), hq);
+                f32x4 z0 = mma32(A2[0], hq, f32x4{b2r[0], b2r[1], b2r[2], b2r[3]});
+                f32x4 z1 = mma32(A2[1], hq, f32x4{b2r[4], b2r[5], b2r[6], b2r[7]});
+                e16x8 o;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if constexpr (JOIN) {
+                        o[j] = (e16)__builtin_fmaf(jsc, (float)rq[j], elu_out(z0[j]) + (float)centre[j]);
+                        o[4 + j] = (e16)__builtin_fmaf(jsc, (float)rq[4 + j], elu_out(z1[j]) + (float)centre[4 + j]);
                     } else {
-                        e16x4 o;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) o[j] = (e16)(val[j] + (float)rq[j]);
-                        *reinterpret_cast<e16x4*>(y + pix * C + 4 * g) = o;
+                        o[j] = (e16)(elu_out(z0[j]) + (float)centre[j]);
+                        o[4 + j] = (e16)(elu_out(z1[j]) + (float)centre[4 + j]);
                     }
                 }
+                if (valid) *reinterpret_cast<e16x8*>(y + pix * C + 8 * g) = o;
             } else {
+                e16x4 hq;
 #pragma unroll
-                for (int j = 0; j < NCH; ++j) val[j] = elu_res(val[j]);
-                if constexpr (C == 32) {
-                    e16x8 hq;
+                for (int j = 0; j < 4; ++j) hq[j] = (e16)val[j];
+                if (SAVE && valid) h1_store(reinterpret_cast<e16x4*>(h1 + pix * C + 4 * g), hq);
+                const f32x4 z = mma16(A2s, __builtin_bit_cast(s16x4, hq), f32x4{b2r[0], b2r[1], b2r[2], b2r[3]});
+                const int colc = c0 + n + D, pxc = (r + D) * G::RW + colc;
+                const e16x4 xc = *reinterpret_cast<const e16x4*>(smem + ((long)pxc * C + 8 * ((g >> 1) ^ cswz<C>(colc)) + 4 * (g & 1)) * 2);
+                e16x4 o;
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) hq[j] = (e16)val[j];
-                    if (SAVE && valid) h1_store(reinterpret_cast<e16x8*>(h1 + pix * C + 8 * g), hq);
-                    f32x4 z0 = mma32(A2[0], hq, f32x4{b2r[0], b2r[1], b2r[2], b2r[3]});
-                    f32x4 z1 = mma32(A2[1], hq, f32x4{b2r[4], b2r[5], b2r[6], b2r[7]});
-                    e16x8 o;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if constexpr (JOIN) {
-                            o[j] = (e16)__builtin_fmaf(jsc, (float)rq[j], elu_out(z0[j]) + (float)centre[j]);
-                            o[4 + j] = (e16)__builtin_fmaf(jsc, (float)rq[4 + j], elu_out(z1[j]) + (float)centre[4 + j]);
-                        } else {
-                            o[j] = (e16)(elu_out(z0[j]) + (float)centre[j]);
-                            o[4 + j] = (e16)(elu_out(z1[j]) + (float)centre[4 + j]);
-                        }
-                    }
-                    if (valid) *reinterpret_cast<e16x8*>(y + pix * C + 8 * g) = o;
-                } else {
-                    e16x4 hq;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) hq[j] = (e16)val[j];
-                    if (SAVE && valid) h1_store(reinterpret_cast<e16x4*>(h1 + pix * C + 4 * g), hq);
-                    const f32x4 z = mma16(A2s, __builtin_bit_cast(s16x4, hq), f32x4{b2r[0], b2r[1], b2r[2], b2r[3]});
-                    const int colc = c0 + n + D, pxc = (r + D) * G::RW + colc;
-                    const e16x4 xc = *reinterpret_cast<const e16x4*>(smem + ((long)pxc * C + 8 * ((g >> 1) ^ cswz<C>(colc)) + 4 * (g & 1)) * 2);
-                    e16x4 o;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) o[j] = JOIN ? (e16)__builtin_fmaf(jsc, (float)rq[j], elu_out(z[j]) + (float)xc[j]) : (e16)(elu_out(z[j]) + (float)xc[j]);
-                    if (valid) *reinterpret_cast<e16x4*>(y + pix * C + 4 * g) = o;
-                }
+                for (int j = 0; j < 4; ++j) o[j] = JOIN ? (e16)__builtin_fmaf(jsc, (float)rq[j], elu_out(z[j]) + (float)xc[j]) : (e16)(elu_out(z[j]) + (float)xc[j]);
+                if (valid) *reinterpret_cast<e16x4*>(y + pix * C + 4 * g) = o;
             }
         }
     }
@@ -334,31 +312,24 @@ template <int C>
 __global__ __launch_bounds__(NT) void k_wrb_bwd_a(const e16* __restrict__ h1, const e16* __restrict__ dy,
                                                   const float* __restrict__ w2, const float* __restrict__ b2,
                                                   e16* __restrict__ da1, float* __restrict__ part, long npix, long ngroups) {
+    static_assert(C == 32, "C = 16 takes the strips (conv_level_bf16.hip)");
     using G = WA<C>;
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = lane & 15, g = lane >> 4;
     constexpr int NCT = C / 16;
-    constexpr int NCH = C == 32 ? 8 : 4;
-    typedef typename std::conditional<C == 32, e16x8, e16x4>::type vec_t;     // a lane's channels of one pixel
+    constexpr int NCH = 8;
+    typedef e16x8 vec_t;                                         // a lane's channels of one pixel
 
     // W2 (rows = output channel) and W2^T (rows = input channel), both with the row order of chan_of
     e16x8 A2[NCT], A2T[NCT];
-    s16x4 A2s, A2Ts;
-    if constexpr (C == 32) {
 #pragma unroll
-        for (int ct = 0; ct < NCT; ++ct)
+    for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                A2[ct][j] = (e16)w2[chan_of<C>(ct, n) * C + 8 * g + j];
-                A2T[ct][j] = (e16)w2[(8 * g + j) * C + chan_of<C>(ct, n)];
-            }
-    } else {
-        e16x4 a, at;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { a[j] = (e16)w2[n * C + 4 * g + j]; at[j] = (e16)w2[(4 * g + j) * C + n]; }
-        A2s = __builtin_bit_cast(s16x4, a); A2Ts = __builtin_bit_cast(s16x4, at);
-    }
+        for (int j = 0; j < 8; ++j) {
+            A2[ct][j] = (e16)w2[chan_of<C>(ct, n) * C + 8 * g + j];
+            A2T[ct][j] = (e16)w2[(8 * g + j) * C + chan_of<C>(ct, n)];
+        }
     float b2r[NCH], db1a[NCH], db2a[NCH];
 #pragma unroll
     for (int j = 0; j < NCH; ++j) { b2r[j] = b2[NCH * g + j]; db1a[j] = 0.f; db2a[j] = 0.f; }
@@ -395,12 +366,8 @@ __global__ __launch_bounds__(NT) void k_wrb_bwd_a(const e16* __restrict__ h1, co
         float hv[NCH], gv[NCH], a1g[NCH];
         vec_t gq, aq;
         f32x4 z[NCT], u[NCT];
-        if constexpr (C == 32) {
-            z[0] = mma32(A2[0], hq, f32x4{b2r[0], b2r[1], b2r[2], b2r[3]});
-            z[1] = mma32(A2[1], hq, f32x4{b2r[4], b2r[5], b2r[6], b2r[7]});
-        } else {
-            z[0] = mma16(A2s, __builtin_bit_cast(s16x4, hq), f32x4{b2r[0], b2r[1], b2r[2], b2r[3]});
-        }
+        z[0] = mma32(A2[0], hq, f32x4{b2r[0], b2r[1], b2r[2], b2r[3]});
+        z[1] = mma32(A2[1], hq, f32x4{b2r[4], b2r[5], b2r[6], b2r[7]});
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
             const float a2 = z[j >> 2][j & 3];
@@ -408,12 +375,8 @@ __global__ __launch_bounds__(NT) void k_wrb_bwd_a(const e16* __restrict__ h1, co
             gq[j] = (e16)gv[j];
             hv[j] = (float)hq[j];
         }
-        if constexpr (C == 32) {
-            u[0] = mma32(A2T[0], gq, f32x4{0.f, 0.f, 0.f, 0.f});
-            u[1] = mma32(A2T[1], gq, f32x4{0.f, 0.f, 0.f, 0.f});
-        } else {
-            u[0] = mma16(A2Ts, __builtin_bit_cast(s16x4, gq), f32x4{0.f, 0.f, 0.f, 0.f});
-        }
+        u[0] = mma32(A2T[0], gq, f32x4{0.f, 0.f, 0.f, 0.f});
+        u[1] = mma32(A2T[1], gq, f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
             a1g[j] = u[j >> 2][j & 3] * elu_dout(hv[j]);
@@ -422,15 +385,12 @@ __global__ __launch_bounds__(NT) void k_wrb_bwd_a(const e16* __restrict__ h1, co
         }
         if (valid) *reinterpret_cast<vec_t*>(da1 + pix * C + NCH * g) = aq;
         // transposition buffers: pixel n, this lane's channels, in 8-byte pieces
-        if constexpr (C == 32) {
+        {
             const uint2* gs = reinterpret_cast<const uint2*>(&gq);
             const uint2* hs = reinterpret_cast<const uint2*>(&hq);
             uint2* gd = reinterpret_cast<uint2*>(tg + n * G::PS + 16 * g);
             uint2* hd = reinterpret_cast<uint2*>(thh + n * G::PS + 16 * g);
             gd[0] = gs[0]; gd[1] = gs[1]; hd[0] = hs[0]; hd[1] = hs[1];
-        } else {
-            *reinterpret_cast<uint2*>(tg + n * G::PS + 8 * g) = __builtin_bit_cast(uint2, gq);
-            *reinterpret_cast<uint2*>(thh + n * G::PS + 8 * g) = __builtin_bit_cast(uint2, hq);
         }
         // dW2[co][ci] += sum over the 16 pixels dA2[co][p] h1[ci][p]: the tiles read back transposed
         // (same wave wrote them: LDS operations of one wave complete in order; the fence only stops the compiler)
@@ -472,123 +432,9 @@ __global__ __launch_bounds__(NT) void k_wrb_bwd_a(const e16* __restrict__ h1, co
     for (int i = tid; i < G::DUMP; i += NT) pw[i] = (all[i] + all[G::DUMP + i]) + (all[2 * G::DUMP + i] + all[3 * G::DUMP + i]);
 }
 
-// ---- 3x3 weight gradient ---------------------------------------------------------------------------------------------
-//   dW1[co][ci][tap] = sum_pix dA1[co][pix] x[ci][pix + tap]     K = pixels, 32 per product (v_mfma_f32_16x16x32_bf16)
-// The x tile (with halo) and the dA1 tile are channel-innermost LDS images filled by LDS-DMA; both operands come out of
-// them by transpose reads (two per operand: pixels 4g..4g+3 and 16+4g..16+4g+3 of the chunk -- the K order is free as long
-// as both operands use the same one).  At C = 32 the two 32-byte halves of a pixel are swapped in every second group of
-// four pixels (a permutation of the DMA sources), which keeps the eight pixels one half-wave reads on different banks.
-// Wave roles: C = 32: ci-tile w & 1, column half w >> 1 (x is the operand read nine times, so it is the one split);
-//             C = 16: column half w & 1, rows of parity w >> 1.
-// Every wave dumps its accumulators [(tap NA + a) 4 + r][lane]; k_wrb_reduce sums the dumps.
-template <int C, int D> struct WG {
-    static constexpr int TH = C == 32 ? 4 : 8, TW = 64;
-    static constexpr int CG = C / 8;
-    static constexpr int RW = TW + 2 * D, ROWS = TH + 2 * D;
-    static constexpr int XP = ROWS * RW * CG, GP = TH * TW * CG;   // 16-byte pieces
-    static constexpr int XPR = (XP + NT - 1) / NT * NT;
-    static constexpr int X_BYTES = XPR * 16, G_BYTES = GP * 16;
-    static constexpr int NA = C / 16;                              // co-tiles a wave accumulates
-    static constexpr int DUMP = 9 * NA * 256;                      // floats per wave
-    static constexpr int LDS_BYTES = X_BYTES + G_BYTES;
-};
-
-template <int C> __device__ __forceinline__ int swz_piece(int q, int cg) { return C == 32 ? (cg ^ (((q >> 2) & 1) << 1)) : cg; }
-
-template <int C, int D>
-__global__ __launch_bounds__(NT) void k_wrb_wgrad(const e16* __restrict__ x, const e16* __restrict__ da1,
-                                                  float* __restrict__ part, int B, int H, int T, int tiles_h, int tiles_t,
-                                                  int ntiles) {
-    using G = WG<C, D>;
-    extern __shared__ __align__(16) unsigned char smem[];
-    unsigned char* xs = smem;
-    unsigned char* gs = smem + G::X_BYTES;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = lane & 15, g = lane >> 4;
-    const int trj = n >> 2, trq = n & 3;
-    constexpr int NA = G::NA;
-    const int cit = C == 32 ? (wave & 1) : 0;                    // ci-tile of this wave
-    const int colh = C == 32 ? (wave >> 1) : (wave & 1);         // 32-pixel column half
-    const int row0 = C == 32 ? 0 : (wave >> 1), rstep = C == 32 ? 1 : 2;
-    f32x4 acc[9][NA];
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-#pragma unroll
-        for (int a = 0; a < NA; ++a) acc[k][a] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const e16* zero = reinterpret_cast<const e16*>(&g_wzero16);
-    for (int v = blockIdx.x; v < ntiles; v += gridDim.x) {
-        int tile = xcd_order(v, ntiles);
-        const int tt = tile % tiles_t; tile /= tiles_t;
-        const int th = tile % tiles_h;
-        const int b = tile / tiles_h, h0 = th * G::TH, t0 = tt * G::TW;
-        const e16* xb = x + (long)b * H * T * C;
-        const e16* gb = da1 + (long)b * H * T * C;
-        __syncthreads();
-        for (int i = wave * 64; i < G::XPR; i += NT) {
-            const int p = i + lane, q = p / G::CG, cg = swz_piece<C>(q, p - q * G::CG);
-            const int row = q / G::RW, px = q - row * G::RW;
-            const int h = h0 - D + row, t = t0 - D + px;
-            const bool ok = p < G::XP && (unsigned)h < (unsigned)H && (unsigned)t < (unsigned)T;
-            glds16(ok ? xb + ((long)h * T + t) * C + cg * 8 : zero, xs + (long)i * 16);
-        }
-        for (int i = wave * 64; i < G::GP; i += NT) {
-            const int p = i + lane, q = p / G::CG, cg = swz_piece<C>(q, p - q * G::CG);
-            const int row = q / G::TW, px = q - row * G::TW;
-            const int h = h0 + row, t = t0 + px;
-            const bool ok = h < H && t < T;
-            glds16(ok ? gb + ((long)h * T + t) * C + cg * 8 : zero, gs + (long)i * 16);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-
-        const int c0 = colh * 32 + 4 * g + trj;                  // first-half pixel whose address this lane supplies
-        for (int r = row0; r < G::TH; r += rstep) {
-            if (h0 + r >= H) break;
-            // dA1 operand(s): co-tiles 0..NA-1
-            e16x8 ga[NA];
-#pragma unroll
-            for (int a = 0; a < NA; ++a) {
-                s16x4 lo, hi;
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const int q = r * G::TW + c0 + 16 * u;
-                    const int half = C == 32 ? ((a ^ ((q >> 2) & 1)) << 5) : 0;
-                    const s16x4 t4 = lds_tr16(gs + (long)q * (C * 2) + half + trq * 8);
-                    if (u == 0) lo = t4; else hi = t4;
-                }
-                ga[a] = __builtin_bit_cast(e16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-            }
-#pragma unroll
-            for (int k = 0; k < 9; ++k) {
-                const int kh = k / 3, kw = k - 3 * kh;
-                s16x4 lo, hi;
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const int q = (r + kh * D) * G::RW + c0 + 16 * u + kw * D;
-                    const int half = C == 32 ? ((cit ^ ((q >> 2) & 1)) << 5) : 0;
-                    const s16x4 t4 = lds_tr16(xs + (long)q * (C * 2) + half + trq * 8);
-                    if (u == 0) lo = t4; else hi = t4;
-                }
-                const e16x8 xq = __builtin_bit_cast(e16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-#pragma unroll
-                for (int a = 0; a < NA; ++a) acc[k][a] = mma32(ga[a], xq, acc[k][a]);
-            }
-        }
-    }
-
-    float* pw = part + ((long)blockIdx.x * 4 + wave) * G::DUMP;
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-#pragma unroll
-        for (int a = 0; a < NA; ++a)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) pw[((k * NA + a) * 4 + r) * 64 + lane] = acc[k][a][r];
-}
-
 // ---- data gradient and weight gradient in ONE pass -----------------------------------------------------------------------
-// k_wrb_conv<..,1> and k_wrb_wgrad both stage the dA1 tile; here it is staged once, next to the x tile, in the layout that serves
-// both access patterns (fswz, wide_common.h): dx = dy + W1^T (*)_D dA1 over the tile by B-operand reads, then
+// A data-gradient kernel and a weight-gradient kernel would both stage the dA1 tile; here it is staged once, next to the x tile, in the
+// layout that serves both access patterns (fswz, wide_common.h): dx = dy + W1^T (*)_D dA1 over the tile by B-operand reads, then
 // dW1[co][ci][tap] += dA1 (x) x(+tap) by transpose reads of the same two images.  dA1 is read from HBM once instead of twice:
 // four tensor passes (dA1, dy, x | dx) for what took five, and one launch less.  No halo beyond D, no recomputation -- the vector
 // work is the sum of the two kernels minus one staging loop (PMC, round 3: both were parked on memory 40-67 % of their life).
@@ -607,14 +453,14 @@ template <int C, int D, int TH, int TW> struct DXW {
     static constexpr int XNPR = (XNP + NT - 1) / NT * NT;
     static constexpr int X_BYTES = XNPR * 16;
     static constexpr int WDUMP = 9 * (C / 16) * 256;
-    // C = 16: the four waves' accumulators are summed through LDS at the end (36.9 KB, more than the two images at dilation 1, 2)
-    static constexpr int LDS_BYTES = (C == 16 && IMG_BYTES + X_BYTES < 4 * WDUMP * 4) ? 4 * WDUMP * 4 : IMG_BYTES + X_BYTES;
+    static constexpr int LDS_BYTES = IMG_BYTES + X_BYTES;
+    static_assert(C == 32, "C = 16 takes the strips (conv_level_bf16.hip)");
     static_assert(TW % 32 == 0, "the K = 32 pixels of a weight-gradient product are 32 consecutive columns");
 };
 
 // SJ (with GOUT): the backward of a skip join on this block's input rides on the epilogue (SkipJ, wide_common.h)
 template <int C, int D, int TH, int TW, bool GOUT = false, bool SJ = false>
-__global__ __launch_bounds__(NT, (GOUT && C == 32) ? 3 : 2) void k_wrb_dxw(const e16* __restrict__ x, const e16* __restrict__ da1, const e16* __restrict__ dy,
+__global__ __launch_bounds__(NT, GOUT ? 3 : 2) void k_wrb_dxw(const e16* __restrict__ x, const e16* __restrict__ da1, const e16* __restrict__ dy,
                                                    const float* __restrict__ w1, e16* __restrict__ dx, float* __restrict__ part_w, int B,
                                                    int H, int T, int tiles_h, int tiles_t, int ntiles, SkipJ sj = SkipJ()) {
     static_assert(!SJ || GOUT, "a skip join rides on the gated epilogue only");
@@ -623,7 +469,7 @@ __global__ __launch_bounds__(NT, (GOUT && C == 32) ? 3 : 2) void k_wrb_dxw(const
     using G = DXW<C, D, TH, TW>;
     using K = WK<C>;
     constexpr int NCT = K::NCT, NK = K::NK, NCH = K::NCH, PB = G::PB;
-    typedef typename std::conditional<C == 32, e16x8, e16x4>::type vec_t;
+    typedef e16x8 vec_t;
     extern __shared__ __align__(16) unsigned char smem[];
     unsigned char* gs = smem;                                    // dA1 (with halo)
     unsigned char* xs = smem + G::IMG_BYTES;                     // x   (the tile's own pixels)
@@ -639,21 +485,15 @@ __global__ __launch_bounds__(NT, (GOUT && C == 32) ? 3 : 2) void k_wrb_dxw(const
             float v[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                int tap, kc;
-                if (C == 32) { tap = k; kc = 8 * g + j; }
-                else { tap = 2 * k + (g >> 1); kc = 8 * (g & 1) + j; }
-                v[j] = tap < 9 ? w1[(kc * C + chan_of<C>(ct, n)) * 9 + (8 - tap)] : 0.f;
+                const int tap = k, kc = 8 * g + j;               // tap and contraction channel of this lane's k = 8 g + j
+                v[j] = tap < 9 ? w1[(kc * C + chan_of<C>(ct, n)) * 9 + (8 - tap)] : 0.f;      // (NK = 9: always a tap)
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) A[k][ct][j] = (e16)v[j];
         }
-    // weight-gradient roles (as in k_wrb_bwd_fused): C = 32: wave = (ci-tile wave & 1, co-tile wave >> 1), all rows and chunks;
-    // C = 16: the waves split the 32-column chunks, then the rows
+    // weight-gradient roles (as in k_wrb_bwd_fused): wave = (ci-tile wave & 1, co-tile wave >> 1), all rows and chunks
     constexpr int NCHK = TW / 32;
-    static_assert(C == 32 || (4 % NCHK == 0), "wave roles");
-    const int cit = C == 32 ? (wave & 1) : 0, aw = C == 32 ? (wave >> 1) : 0;
-    const int ch0 = C == 32 ? 0 : wave % NCHK, rpar = C == 32 ? 0 : wave / NCHK;
-    constexpr int CHSTEP = C == 32 ? 1 : NCHK, RSTEP = C == 32 ? 1 : 4 / NCHK;
+    const int cit = wave & 1, aw = wave >> 1;
     f32x4 wacc[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) wacc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -734,8 +574,7 @@ __global__ __launch_bounds__(NT, (GOUT && C == 32) ? 3 : 2) void k_wrb_dxw(const
 #pragma unroll
                 for (int j = 0; j < NCH; ++j) sum[j] = acc[j >> 2][j & 3] + (float)rq[j];
                 asm volatile("" ::: "memory");
-                const vec_t xq = *reinterpret_cast<const vec_t*>(xs + (r * TW + c) * PB + 16 * ((C == 32 ? g : (g >> 1)) ^ fswz<C>(c)) +
-                                                                 (C == 32 ? 0 : 8 * (g & 1)));
+                const vec_t xq = *reinterpret_cast<const vec_t*>(xs + (r * TW + c) * PB + 16 * (g ^ fswz<C>(c)));
                 if constexpr (SJ) {
                     float add[NCH], dot = 0.f;
                     skipj_terms<vec_t, NCH>(cur.sg0, cur.sg1, sj.half != 0, xq, sjw, add, dot);
@@ -773,16 +612,16 @@ __global__ __launch_bounds__(NT, (GOUT && C == 32) ? 3 : 2) void k_wrb_dxw(const
         }
 
         // ---- dW1, K = pixels: 32 consecutive columns of a row per product, both operands by transpose reads ----
-        for (int r = rpar; r < TH; r += RSTEP) {
+        for (int r = 0; r < TH; ++r) {
             if (h0 + r >= H) break;
 #pragma unroll
-            for (int ch = ch0; ch < NCHK; ch += CHSTEP) {
+            for (int ch = 0; ch < NCHK; ++ch) {
                 s16x4 lo, hi;
                 // indexed by the pixel of x: B = x at (r, 32 ch ..) of its halo-free image, A = dA1 at row r + (2 - kh) D, column (2 - kw) D + ..
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
                     const int xc = ch * 32 + 4 * g + trj + 16 * u;
-                    const s16x4 t4 = lds_tr16(xs + (r * TW + xc) * PB + 16 * (((C == 32 ? 2 * cit : 0) + (trq >> 1)) ^ fswz<C>(xc)) + 8 * (trq & 1));
+                    const s16x4 t4 = lds_tr16(xs + (r * TW + xc) * PB + 16 * ((2 * cit + (trq >> 1)) ^ fswz<C>(xc)) + 8 * (trq & 1));
                     if (u == 0) lo = t4; else hi = t4;
                 }
                 const e16x8 xq = __builtin_bit_cast(e16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
@@ -793,7 +632,7 @@ __global__ __launch_bounds__(NT, (GOUT && C == 32) ? 3 : 2) void k_wrb_dxw(const
                     for (int u = 0; u < 2; ++u) {
                         const int cc = (2 - kw) * D + ch * 32 + 4 * g + trj + 16 * u;
                         const s16x4 t4 = lds_tr16(gs + ((r + (2 - kh) * D) * G::IW + cc) * PB +
-                                                  16 * (((C == 32 ? 2 * aw : 0) + (trq >> 1)) ^ fswz<C>(cc)) + 8 * (trq & 1));
+                                                  16 * ((2 * aw + (trq >> 1)) ^ fswz<C>(cc)) + 8 * (trq & 1));
                         if (u == 0) lo = t4; else hi = t4;
                     }
                     wacc[k] = mma32(__builtin_bit_cast(e16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7)), xq, wacc[k]);
@@ -802,25 +641,11 @@ __global__ __launch_bounds__(NT, (GOUT && C == 32) ? 3 : 2) void k_wrb_dxw(const
         }
     }
     if constexpr (SJ) skipj_finish(sjdot, sj);
-    if constexpr (C == 32) {
-        float* pw = part_w + ((long)blockIdx.x * 4 + wave) * G::WDUMP;
+    float* pw = part_w + ((long)blockIdx.x * 4 + wave) * G::WDUMP;
 #pragma unroll
-        for (int k = 0; k < 9; ++k)
+    for (int k = 0; k < 9; ++k)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) pw[((k * NCT + aw) * 4 + r) * 64 + lane] = wacc[k][r];   // only this wave's co-tile (RedArgs::split_a)
-    } else {
-        // C = 16: the four waves hold the same (co, ci, tap) elements: summed through LDS, ONE dump per workgroup (wave slot 0) --
-        // the reduce kernel reads a quarter of the bytes (RedArgs::one_dump)
-        __syncthreads();
-        float* red = reinterpret_cast<float*>(smem);
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) red[wave * G::WDUMP + (k * 4 + r) * 64 + lane] = wacc[k][r];
-        __syncthreads();
-        float* pw = part_w + (long)blockIdx.x * 4 * G::WDUMP;
-        for (int i = tid; i < G::WDUMP; i += NT) pw[i] = (red[i] + red[G::WDUMP + i]) + (red[2 * G::WDUMP + i] + red[3 * G::WDUMP + i]);
-    }
+        for (int r = 0; r < 4; ++r) pw[((k * NCT + aw) * 4 + r) * 64 + lane] = wacc[k][r];   // only this wave's co-tile (RedArgs::split_a)
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------
@@ -836,7 +661,7 @@ int launch_conv(const e16* x, const float* w1, const float* b1, const float* w2,
     if (int rc = raise_lds(kern, G::LDS_BYTES, once)) return rc;
     // registers admit two workgroups per CU at C = 32 (forward) whatever the LDS would hold: do not launch a third that only runs
     // after the first two have finished (a tail on a third of the chip)
-    const int cap = (C == 32 && MODE != 1 && per_cu > 2) ? 2 : per_cu;
+    const int cap = (C == 32 && per_cu > 2) ? 2 : per_cu;
     hipLaunchKernelGGL(kern, dim3(grid_for(ntiles, G::LDS_BYTES, cap)), dim3(NT), G::LDS_BYTES, st, x, w1, b1, w2, b2, res, y, h1,
                        B, H, T, tiles_h, tiles_t, ntiles, jw, jB);
     TT_LAUNCH_CHECK();
@@ -850,10 +675,10 @@ int launch_dxw(const e16* x, const e16* da1, const e16* dy, const float* w1, e16
                float* dw1, float* db1, float* dw2, float* db2, int B, int H, int T, hipStream_t st, LevelCtx* ctx) {
     using X = DXW<C, D, TH, TW>;
     const int tiles_h = (H + TH - 1) / TH, tiles_t = (T + TW - 1) / TW, ntiles = B * tiles_h * tiles_t;
-    static const int x_per_cu = tt_tune("TTRAP_DXW_PER_CU", C == 32 ? 3 : 4);      // registers: 165 / 113 VGPRs
+    static const int x_per_cu = tt_tune("TTRAP_DXW_PER_CU", 3);                    // registers: 165 VGPRs
     int gx = grid_for(ntiles, X::LDS_BYTES, x_per_cu);
     if (gx > MAX_W_WG) gx = MAX_W_WG;
-    const FirstForm form = first_form(ctx, D, true);             // a level's first block: dx leaves gated (k_nrb_bwd_fused, GOUT)
+    const FirstForm form = first_form(ctx, D);                   // a level's first block: dx leaves gated (k_nrb_bwd_fused, GOUT)
     if constexpr (D == 1) {
         if (form == FirstForm::Riding) {
             static AttrOnce once_j;
@@ -874,76 +699,52 @@ int launch_dxw(const e16* x, const e16* da1, const e16* dy, const float* w1, e16
         hipLaunchKernelGGL(kx, dim3(gx), dim3(NT), X::LDS_BYTES, st, x, da1, dy, w1, dx, part_w, B, H, T, tiles_h, tiles_t, ntiles, SkipJ());
     }
     TT_LAUNCH_CHECK();
-    RedArgs ra{part_w, gx, part_a, grid_a, dw1, db1, dw2, db2, C == 32 ? 1 : 0, C == 32 ? 0 : 1};
+    RedArgs ra{part_w, gx, part_a, grid_a, dw1, db1, dw2, db2, 1, 0};
     constexpr int total = 9 * C * C + C * C + 2 * C;
     return reduce_or_defer(ctx, k_wrb_reduce<C>, total, ra, st);
 }
 
 // One-pass backward (k_wrb_bwds, conv_level_bf16.hip: column strips, dA1 in a rolling LDS ring, 4 tensors of HBM traffic) or the
-// per-stage kernels below (7 tensors): TTRAP_WBWD1 = 0 / 1 forces one of them for every width and dilation, 16 / 32 the one-pass
-// kernel at that width only; unset = the measured choice.  Round 4, measured INSIDE the 64-clip train step (bench.py --timed-only, same
-// box, back to back; profiles/r04_wbwd1_step_ab.txt), average call: C = 16 0.418 -> 0.376 ms (taken: step 57.64 -> 56.75 ms);
-// C = 32 0.427 -> 0.495 ms (not taken).  The isolated micro-benchmark (tools/kb_level.py) had the C = 32 strips level with the
-// per-stage kernels (0.450 / 0.458 / 0.453 vs 0.465 / 0.430 / 0.464 ms): inside the step the per-stage path finds dy (just written by
-// the next block's backward) and its own dA1 in the 256 MB memory-side cache, so its extra passes cost less than their bytes, while
+// per-stage kernels below (7 tensors): the measured choice, C = 16 the strips, C = 32 per stage.  Round 4, measured INSIDE the 64-clip train
+// step (bench.py --timed-only, same box, back to back; profiles/r04_wbwd1_step_ab.txt), average call: C = 16 0.418 -> 0.376 ms (taken: step
+// 57.64 -> 56.75 ms); C = 32 0.427 -> 0.495 ms (not taken).  The isolated micro-benchmark (tools/kb_level.py) had the C = 32 strips level
+// with the per-stage kernels (0.450 / 0.458 / 0.453 vs 0.465 / 0.430 / 0.464 ms): inside the step the per-stage path finds dy (just written
+// by the next block's backward) and its own dA1 in the 256 MB memory-side cache, so its extra passes cost less than their bytes, while
 // the one-pass kernel runs at two to three waves per SIMD (168 registers) with the vector ALUs 39 % and the matrix pipe 19 % busy.
-inline int onepass_choice(int C, int D) {
-    static const int forced = tt_switch("TTRAP_WBWD1", -1);       // 0 / 1: never / always; 16 / 32: at that width only
-    if (forced == 16 || forced == 32) return C == forced ? 1 : 0;
-    if (forced >= 0) return forced ? 1 : 0;
-    (void)D;
-    return C == 16 ? 1 : 0;
-}
+// (The switch that forced either route at either width went with the per-stage kernels' C = 16 instantiations.)
+constexpr bool onepass_choice(int C, int /*D*/) { return C == 16; }
 
 template <int C, int D>
 int launch_bwd(const e16* x, const e16* h1, const e16* dy, const float* w1, const float* w2, const float* b2,
                e16* dx, float* dw1, float* db1, float* dw2, float* db2, unsigned char* ws, int B, int H, int T,
                hipStream_t st, LevelCtx* ctx) {
-    if (onepass_choice(C, D)) return ttx_wide_rb_bwd_onepass(ctx, x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, C, H, T, D, st);
-    const long npix = (long)B * H * T;
-    e16* da1 = reinterpret_cast<e16*>(ws);
-    float* part_a = reinterpret_cast<float*>(ws + ((npix * C * 2 + 255) / 256) * 256);
-    float* part_w = part_a + (long)MAX_A_WG * WA<C>::DUMP;
-    // pointwise chain
-    using G = WA<C>;
-    static AttrOnce once;
-    auto kern = k_wrb_bwd_a<C>;
-    if (int rc = raise_lds(kern, G::LDS_BYTES, once)) return rc;
-    const long ngroups = (npix + 15) / 16;
-    const long want = (ngroups + 3) / 4;
-    static const int a_per_cu = tt_tune("TTRAP_BWDA_PER_CU", 4);
-    int grid = (int)(want < (long)a_per_cu * tt_cus() ? want : (long)a_per_cu * tt_cus());
-    if (grid > MAX_A_WG) grid = MAX_A_WG;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), G::LDS_BYTES, st, h1, dy, w2, b2, da1, part_a, npix, ngroups);
-    TT_LAUNCH_CHECK();
-    // data gradient + weight gradient in one pass (TTRAP_DXW=0: the two separate kernels)
-    static const int dxw = tt_switch("TTRAP_DXW", 1);
-    if (dxw) {
-        // tiles 8 x 32 at both widths (round 3, per call at the bench shape, separate kernels -> merged: C = 32 0.486 / 0.485 / 0.521 ->
-        // 0.413 / 0.443 / 0.454 ms; C = 16 0.469 / 0.469 / 0.474 -> 0.430 / 0.431 / 0.451 ms; 8 x 64 tiles at C = 16 lose at
-        // dilation 2, 3 (0.50 ms: two workgroups per CU); 16 x 32 tiles at C = 16: 0.431 / 0.439 / 0.496 ms)
-        // C = 32, dilation 2: two images of 12 x 36 pixels are 55 KB = two workgroups per CU; 6-row tiles (49 KB) admit the third:
+    if constexpr (onepass_choice(C, D)) {
+        return ttx_wide_rb_bwd_onepass(ctx, x, h1, dy, w1, w2, b2, dx, dw1, db1, dw2, db2, ws, B, C, H, T, D, st);
+    } else {
+        const long npix = (long)B * H * T;
+        e16* da1 = reinterpret_cast<e16*>(ws);
+        float* part_a = reinterpret_cast<float*>(ws + ((npix * C * 2 + 255) / 256) * 256);
+        float* part_w = part_a + (long)MAX_A_WG * WA<C>::DUMP;
+        // pointwise chain
+        using G = WA<C>;
+        static AttrOnce once;
+        auto kern = k_wrb_bwd_a<C>;
+        if (int rc = raise_lds(kern, G::LDS_BYTES, once)) return rc;
+        const long ngroups = (npix + 15) / 16;
+        const long want = (ngroups + 3) / 4;
+        static const int a_per_cu = tt_tune("TTRAP_BWDA_PER_CU", 4);
+        int grid = (int)(want < (long)a_per_cu * tt_cus() ? want : (long)a_per_cu * tt_cus());
+        if (grid > MAX_A_WG) grid = MAX_A_WG;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), G::LDS_BYTES, st, h1, dy, w2, b2, da1, part_a, npix, ngroups);
+        TT_LAUNCH_CHECK();
+        // data gradient + weight gradient in one pass, tiles 8 x 32 (round 3, per call at the bench shape, a kernel each -> merged:
+        // 0.486 / 0.485 / 0.521 -> 0.413 / 0.443 / 0.454 ms).
+        // Dilation 2: two images of 12 x 36 pixels are 55 KB = two workgroups per CU; 6-row tiles (49 KB) admit the third:
         // 0.456 -> 0.427 ms per call.  Dilation 3 (68 KB; 4-row tiles 49 KB): no change, 0.467 ms either way -- 8 rows kept.
         // Round 5: the x tile without halo: 8-row tiles fit three workgroups per CU at every dilation
-        // (the round-3 / 4 form -- x with halo, 6-row tiles at C = 32 / dilation 2 -- is gone: profiles/r05_dxw_xh_x3n_shapes_ab.txt)
+        // (the round-3 / 4 form -- x with halo, 6-row tiles at dilation 2 -- is gone: profiles/r05_dxw_xh_x3n_shapes_ab.txt)
         return launch_dxw<C, D, 8, 32>(x, da1, dy, w1, dx, part_w, part_a, grid, dw1, db1, dw2, db2, B, H, T, st, ctx);
     }
-    // data gradient
-    if (int rc = launch_conv<C, D, 1, false>(da1, w1, nullptr, nullptr, nullptr, dy, dx, nullptr, B, H, T, st)) return rc;
-    // weight gradient
-    using W = WG<C, D>;
-    static AttrOnce once_w;
-    auto kw = k_wrb_wgrad<C, D>;
-    if (int rc = raise_lds(kw, W::LDS_BYTES, once_w)) return rc;
-    const int tiles_h = (H + W::TH - 1) / W::TH, tiles_t = (T + W::TW - 1) / W::TW, ntiles = B * tiles_h * tiles_t;
-    static const int w_per_cu = tt_tune("TTRAP_WGRAD_PER_CU", 2);
-    int gw = grid_for(ntiles, W::LDS_BYTES, w_per_cu);
-    if (gw > MAX_W_WG) gw = MAX_W_WG;
-    hipLaunchKernelGGL(kw, dim3(gw), dim3(NT), W::LDS_BYTES, st, x, da1, part_w, B, H, T, tiles_h, tiles_t, ntiles);
-    TT_LAUNCH_CHECK();
-    RedArgs ra{part_w, gw, part_a, grid, dw1, db1, dw2, db2};
-    constexpr int total = 9 * C * C + C * C + 2 * C;
-    return reduce_or_defer(ctx, k_wrb_reduce<C>, total, ra, st);
 }
 
 template <int C>
@@ -1004,13 +805,14 @@ template <int C, int D> struct NTl {
 
 // C = 8 forward: capped at 168 VGPRs (three waves per SIMD; 208 otherwise): 0.194 / 0.190 / 0.195 -> 0.187 / 0.186 / 0.189 ms (library A/B, round 3)
 template <int C, int D, int MODE, bool SAVE>
-__global__ __launch_bounds__(NT, (C == 8 && MODE != 1) ? 3 : 1) void k_nrb_conv(const e16* __restrict__ x, const float* __restrict__ w1,
+__global__ __launch_bounds__(NT, C == 8 ? 3 : 1) void k_nrb_conv(const e16* __restrict__ x, const float* __restrict__ w1,
                                                  const float* __restrict__ b1, const float* __restrict__ w2,
                                                  const float* __restrict__ b2, const e16* __restrict__ res,
                                                  e16* __restrict__ y, e16* __restrict__ h1, int B, int H, int T,
                                                  int tiles_h, int tiles_t, int ntiles, const float* __restrict__ jw, int jB) {
     using G = NTl<C, D>;
-    constexpr bool FWD = MODE != 1, JOIN = MODE == 2;            // MODE 2: the forward with a skip join in its epilogue (see k_wrb_conv)
+    static_assert(MODE == 0 || MODE == 2, "the block forward, plain or with a skip join");
+    constexpr bool JOIN = MODE == 2;                             // MODE 2: the forward with a skip join in its epilogue (see k_wrb_conv)
     float jsc = 0.f;
     if constexpr (JOIN) jsc = jw ? jw[0] : 1.f;
     typedef typename VecOf<C>::type vec_t;
@@ -1031,27 +833,25 @@ __global__ __launch_bounds__(NT, (C == 8 && MODE != 1) ? 3 : 1) void k_nrb_conv(
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int mo = 4 * ob + i4, kc = 4 * kb + k;
-                    const float wv = FWD ? w1[(mo * C + kc) * 9 + tap] : w1[(kc * C + mo) * 9 + (8 - tap)];
-                    if (FWD) chk = poison_acc(chk, wv);
+                    const float wv = w1[(mo * C + kc) * 9 + tap];
+                    chk = poison_acc(chk, wv);
                     t[k] = (e16)wv;
                 }
                 A[tap][ob][kb] = __builtin_bit_cast(s16x4, t);
             }
     float b1r[C], b2r[C];
-    if constexpr (FWD) {
 #pragma unroll
-        for (int ob = 0; ob < NB; ++ob)
+    for (int ob = 0; ob < NB; ++ob)
 #pragma unroll
-            for (int kb = 0; kb < NB; ++kb) {
-                e16x4 t;
+        for (int kb = 0; kb < NB; ++kb) {
+            e16x4 t;
 #pragma unroll
-                for (int k = 0; k < 4; ++k) { const float wv = w2[(4 * ob + i4) * C + 4 * kb + k]; chk = poison_acc(chk, wv); t[k] = (e16)wv; }
-                A2[ob][kb] = __builtin_bit_cast(s16x4, t);
-            }
+            for (int k = 0; k < 4; ++k) { const float wv = w2[(4 * ob + i4) * C + 4 * kb + k]; chk = poison_acc(chk, wv); t[k] = (e16)wv; }
+            A2[ob][kb] = __builtin_bit_cast(s16x4, t);
+        }
 #pragma unroll
-        for (int c = 0; c < C; ++c) { b1r[c] = b1[c]; b2r[c] = b2[c]; chk = poison_acc(poison_acc(chk, b1r[c]), b2r[c]); }
-    }
-    const bool poisoned = FWD && params_poisoned(chk);          // see k_wrb_conv (a non-finite join weight propagates through the fma by itself)
+    for (int c = 0; c < C; ++c) { b1r[c] = b1[c]; b2r[c] = b2[c]; chk = poison_acc(poison_acc(chk, b1r[c]), b2r[c]); }
+    const bool poisoned = params_poisoned(chk);                 // see k_wrb_conv (a non-finite join weight propagates through the fma by itself)
 
     const e16* zero = reinterpret_cast<const e16*>(&g_wzero16);
     for (int v = blockIdx.x; v < ntiles; v += gridDim.x) {
@@ -1099,13 +899,9 @@ __global__ __launch_bounds__(NT, (C == 8 && MODE != 1) ? 3 : 1) void k_nrb_conv(
                 continue;
             }
             vec_t rq;
-            if constexpr (MODE == 1) rq = *reinterpret_cast<const vec_t*>(res + (valid ? pix : pix - (t - (T - 1))) * C);
-            f32x4 acc[NB];
+            f32x4 acc[NB];                                       // the bias enters as the accumulator's initial value
 #pragma unroll
-            for (int ob = 0; ob < NB; ++ob) {
-                if constexpr (FWD) acc[ob] = f32x4{b1r[4 * ob], b1r[4 * ob + 1], b1r[4 * ob + 2], b1r[4 * ob + 3]};
-                else acc[ob] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
+            for (int ob = 0; ob < NB; ++ob) acc[ob] = f32x4{b1r[4 * ob], b1r[4 * ob + 1], b1r[4 * ob + 2], b1r[4 * ob + 3]};
             vec_t centre;
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
@@ -1123,207 +919,23 @@ __global__ __launch_bounds__(NT, (C == 8 && MODE != 1) ? 3 : 1) void k_nrb_conv(
                 const int hn = h + 4 < H ? h + 4 : H - 1;
                 jq = *reinterpret_cast<const vec_t*>(jrow + (long)hn * T * C);
             }
-            vec_t o;
-            if constexpr (MODE == 1) {
+            vec_t o, hq;
 #pragma unroll
-                for (int c = 0; c < C; ++c) o[c] = (e16)(acc[c >> 2][c & 3] + (float)rq[c]);
-            } else {
-                vec_t hq;
+            for (int c = 0; c < C; ++c) hq[c] = (e16)elu_res(acc[c >> 2][c & 3]);
+            if (SAVE && valid) h1_store(reinterpret_cast<vec_t*>(h1 + pix * C), hq);
+            f32x4 z[NB];
 #pragma unroll
-                for (int c = 0; c < C; ++c) hq[c] = (e16)elu_res(acc[c >> 2][c & 3]);
-                if (SAVE && valid) h1_store(reinterpret_cast<vec_t*>(h1 + pix * C), hq);
-                f32x4 z[NB];
+            for (int ob = 0; ob < NB; ++ob) {
+                z[ob] = f32x4{b2r[4 * ob], b2r[4 * ob + 1], b2r[4 * ob + 2], b2r[4 * ob + 3]};
 #pragma unroll
-                for (int ob = 0; ob < NB; ++ob) {
-                    z[ob] = f32x4{b2r[4 * ob], b2r[4 * ob + 1], b2r[4 * ob + 2], b2r[4 * ob + 3]};
-#pragma unroll
-                    for (int kb = 0; kb < NB; ++kb) z[ob] = mma4(A2[ob][kb], chunk_of<C>(hq, kb), z[ob]);
-                }
-#pragma unroll
-                for (int c = 0; c < C; ++c)
-                    o[c] = JOIN ? (e16)__builtin_fmaf(jsc, (float)rq[c], elu_out(z[c >> 2][c & 3]) + (float)centre[c]) : (e16)(elu_out(z[c >> 2][c & 3]) + (float)centre[c]);
+                for (int kb = 0; kb < NB; ++kb) z[ob] = mma4(A2[ob][kb], chunk_of<C>(hq, kb), z[ob]);
             }
+#pragma unroll
+            for (int c = 0; c < C; ++c)
+                o[c] = JOIN ? (e16)__builtin_fmaf(jsc, (float)rq[c], elu_out(z[c >> 2][c & 3]) + (float)centre[c]) : (e16)(elu_out(z[c >> 2][c & 3]) + (float)centre[c]);
             if (valid) *reinterpret_cast<vec_t*>(y + pix * C) = o;
         }
     }
-}
-
-// Pointwise chain of the backward, lane = pixel.  dW2 is a per-lane outer product (C^2 fused multiply-adds per pixel),
-// reduced over the wave by shuffles once at the end.  One dump [dW2 co*C+ci][db1][db2] per workgroup.
-template <int C>
-__global__ __launch_bounds__(NT) void k_nrb_bwd_a(const e16* __restrict__ h1, const e16* __restrict__ dy,
-                                                  const float* __restrict__ w2, const float* __restrict__ b2,
-                                                  e16* __restrict__ da1, float* __restrict__ part, long npix, long ngroups) {
-    typedef typename VecOf<C>::type vec_t;
-    constexpr int NB = C / 4, DUMP = C * C + 2 * C;
-    __shared__ float red[4][DUMP];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i4 = lane & 3;
-    s16x4 A2[NB][NB], A2T[NB][NB];
-#pragma unroll
-    for (int ob = 0; ob < NB; ++ob)
-#pragma unroll
-        for (int kb = 0; kb < NB; ++kb) {
-            e16x4 a, at;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                a[k] = (e16)w2[(4 * ob + i4) * C + 4 * kb + k];
-                at[k] = (e16)w2[(4 * kb + k) * C + 4 * ob + i4];
-            }
-            A2[ob][kb] = __builtin_bit_cast(s16x4, a); A2T[ob][kb] = __builtin_bit_cast(s16x4, at);
-        }
-    float b2r[C], acc[DUMP];
-#pragma unroll
-    for (int c = 0; c < C; ++c) b2r[c] = b2[c];
-#pragma unroll
-    for (int e = 0; e < DUMP; ++e) acc[e] = 0.f;
-
-    vec_t zero_v;
-#pragma unroll
-    for (int c = 0; c < C; ++c) zero_v[c] = (e16)0.f;
-    const long gstride = (long)gridDim.x * 4;
-    long grp = (long)blockIdx.x * 4 + wave;
-    vec_t hq = zero_v, dq = zero_v;
-    if (grp < ngroups && grp * 64 + lane < npix) {
-        hq = *reinterpret_cast<const vec_t*>(h1 + (grp * 64 + lane) * C);
-        dq = *reinterpret_cast<const vec_t*>(dy + (grp * 64 + lane) * C);
-    }
-    for (; grp < ngroups; grp += gstride) {
-        const long pix = grp * 64 + lane, pn = (grp + gstride) * 64 + lane;
-        vec_t hq_n = zero_v, dq_n = zero_v;
-        if (grp + gstride < ngroups && pn < npix) {
-            hq_n = *reinterpret_cast<const vec_t*>(h1 + pn * C);
-            dq_n = *reinterpret_cast<const vec_t*>(dy + pn * C);
-        }
-        f32x4 z[NB], u[NB];
-#pragma unroll
-        for (int ob = 0; ob < NB; ++ob) {
-            z[ob] = f32x4{b2r[4 * ob], b2r[4 * ob + 1], b2r[4 * ob + 2], b2r[4 * ob + 3]};
-#pragma unroll
-            for (int kb = 0; kb < NB; ++kb) z[ob] = mma4(A2[ob][kb], chunk_of<C>(hq, kb), z[ob]);
-        }
-        float gv[C], hv[C], gr[C];
-        vec_t gq, aq;
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const float a2 = z[c >> 2][c & 3];
-            gv[c] = (float)dq[c] * elu_dpre(a2);
-            gq[c] = (e16)gv[c];
-            gr[c] = (float)gq[c];
-            hv[c] = (float)hq[c];
-        }
-#pragma unroll
-        for (int ob = 0; ob < NB; ++ob) {
-            u[ob] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kb = 0; kb < NB; ++kb) u[ob] = mma4(A2T[ob][kb], chunk_of<C>(gq, kb), u[ob]);
-        }
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const float a1 = u[c >> 2][c & 3] * elu_dout(hv[c]);
-            aq[c] = (e16)a1;
-            acc[C * C + c] += a1; acc[C * C + C + c] += gv[c];       // invalid pixels contribute zeros
-        }
-        if (pix < npix) *reinterpret_cast<vec_t*>(da1 + pix * C) = aq;
-#pragma unroll
-        for (int co = 0; co < C; ++co)
-#pragma unroll
-            for (int ci = 0; ci < C; ++ci)     // plain v_fmac_f32, spelled out (the SLP-vectorised form of this pattern was the run-to-run different one of round 3: profiles/r04_isa_*)
-                asm("v_fmac_f32 %0, %1, %2" : "+v"(acc[co * C + ci]) : "v"(gr[co]), "v"(hv[ci]));
-        hq = hq_n; dq = dq_n;
-    }
-#pragma unroll
-    for (int e = 0; e < DUMP; ++e) {
-        float sv = acc[e];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sv += __shfl_xor(sv, o, 64);
-        if (lane == 0) red[wave][e] = sv;
-    }
-    __syncthreads();
-    float* pw = part + (long)blockIdx.x * DUMP;
-    for (int e = tid; e < DUMP; e += NT) pw[e] = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]);
-}
-
-// 3x3 weight gradient of the narrow levels.  A row of the channel-innermost image is read as a flat run of 32-byte slots
-// (16 bf16 = 2 pixels at C = 8, 4 pixels at C = 4); the transpose reads then deliver, per lane, "column" (pixel-in-slot s,
-// channel c) = 4 s.. over the slots that are the K of the product.  D[(s,c)][(s',c')] mixes the pixels of a slot; only the
-// diagonal blocks s = s' pair a gradient pixel with its own input pixel -- k_nrb_reduce adds exactly those.
-template <int C, int D> struct NG {
-    static constexpr int TH = 8, TW = 128;
-    static constexpr int PXB = C * 2, PPP = 16 / PXB;
-    static constexpr int DP = (D + PPP - 1) / PPP * PPP;
-    static constexpr int RW = TW + 2 * DP, ROWS = TH + 2 * D;
-    static constexpr int XP = ROWS * RW / PPP, GP = TH * TW / PPP;
-    static constexpr int XPR = (XP + NT - 1) / NT * NT, GPR = (GP + NT - 1) / NT * NT;
-    static constexpr int X_BYTES = XPR * 16, G_BYTES = GPR * 16;
-    static constexpr int CHUNKS = TW * PXB / 1024;               // 1024-byte chunks (32 slots) per row: 1 (C = 4), 2 (C = 8)
-    static constexpr int DUMP = 9 * 256;
-    static constexpr int LDS_BYTES = X_BYTES + G_BYTES;
-};
-
-template <int C, int D>
-__global__ __launch_bounds__(NT) void k_nrb_wgrad(const e16* __restrict__ x, const e16* __restrict__ da1,
-                                                  float* __restrict__ part, int B, int H, int T, int tiles_h, int tiles_t,
-                                                  int ntiles) {
-    using G = NG<C, D>;
-    extern __shared__ __align__(16) unsigned char smem[];
-    unsigned char* xs = smem;
-    unsigned char* gs = smem + G::X_BYTES;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = lane & 15, g = lane >> 4;
-    const int trj = n >> 2, trq = n & 3;
-    const int chunk = wave % G::CHUNKS, row0 = wave / G::CHUNKS;
-    constexpr int RSTEP = 4 / G::CHUNKS;
-    f32x4 acc[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) acc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const e16* zero = reinterpret_cast<const e16*>(&g_wzero16);
-    for (int v = blockIdx.x; v < ntiles; v += gridDim.x) {
-        int tile = xcd_order(v, ntiles);
-        const int tt = tile % tiles_t; tile /= tiles_t;
-        const int th = tile % tiles_h;
-        const int b = tile / tiles_h, h0 = th * G::TH, t0 = tt * G::TW;
-        const e16* xb = x + (long)b * H * T * C;
-        const e16* gb = da1 + (long)b * H * T * C;
-        __syncthreads();
-        for (int i = wave * 64; i < G::XPR; i += NT) {
-            const int p = i + lane, q = p * G::PPP;
-            const int row = q / G::RW, px = q - row * G::RW;
-            const int h = h0 - D + row, t = t0 - G::DP + px;
-            const bool ok = p < G::XP && (unsigned)h < (unsigned)H && (unsigned)t < (unsigned)T;
-            glds16(ok ? xb + ((long)h * T + t) * C : zero, xs + (long)i * 16);
-        }
-        for (int i = wave * 64; i < G::GPR; i += NT) {
-            const int p = i + lane, q = p * G::PPP;
-            const int row = q / G::TW, px = q - row * G::TW;
-            const int h = h0 + row, t = t0 + px;
-            const bool ok = p < G::GP && h < H && t < T;
-            glds16(ok ? gb + ((long)h * T + t) * C : zero, gs + (long)i * 16);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-
-        const int so = chunk * 1024 + 32 * (4 * g + trj) + 8 * trq;      // byte offset inside a row of this lane's first slot
-        for (int r = row0; r < G::TH; r += RSTEP) {
-            if (h0 + r >= H) break;
-            const unsigned char* gp = gs + (long)r * (G::TW * G::PXB) + so;
-            const s16x4 glo = lds_tr16(gp), ghi = lds_tr16(gp + 512);
-            const e16x8 ga = __builtin_bit_cast(e16x8, __builtin_shufflevector(glo, ghi, 0, 1, 2, 3, 4, 5, 6, 7));
-#pragma unroll
-            for (int k = 0; k < 9; ++k) {
-                const int kh = k / 3, kw = k - 3 * kh;
-                const unsigned char* xp = xs + (long)(r + kh * D) * (G::RW * G::PXB) + (G::DP + (kw - 1) * D) * G::PXB + so;
-                const s16x4 lo = lds_tr16(xp), hi = lds_tr16(xp + 512);
-                acc[k] = mma32(ga, __builtin_bit_cast(e16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7)), acc[k]);
-            }
-        }
-    }
-    float* pw = part + ((long)blockIdx.x * 4 + wave) * G::DUMP;
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pw[(k * 4 + r) * 64 + lane] = acc[k][r];
 }
 
 // ---- the whole backward of a narrow block in ONE pass ---------------------------------------------------------------------
@@ -1570,7 +1182,7 @@ __global__ __launch_bounds__(NT, C == 8 ? 2 : TT_NBF2_MINW4) void k_nrb_bwd_fuse
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // x has had all of phase 1 to arrive
         __syncthreads();
 
-        // ---- phase 2a: dx = dy + W1^T (*) dA1 (k_nrb_conv, MODE 1, operands from LDS) ----
+        // ---- phase 2a: dx = dy + W1^T (*) dA1 (k_nrb_conv's product loop with W1 transposed and the taps reversed, operands from LDS) ----
         {
             s16x4 A[9][NB][NB];
 #pragma unroll
@@ -1625,7 +1237,7 @@ __global__ __launch_bounds__(NT, C == 8 ? 2 : TT_NBF2_MINW4) void k_nrb_bwd_fuse
         }
 
         // ---- phase 2b: dW1[tap] = sum over the tile's own pixels q of x[q] (x) dA1[q - off(tap)]: x from its halo-free image, dA1 at
-        //      row r + (2 - kh) D, column DP - (kw - 1) D of the halo'd one; 32-byte slots by transpose reads as in k_nrb_wgrad (the two
+        //      row r + (2 - kh) D, column DP - (kw - 1) D of the halo'd one; 32-byte slots by transpose reads (the two
         //      K halves are the two halves of a row at C = 8, two consecutive rows at C = 4) ----
         {
             constexpr int ROWB = G::RW * G::PXB;                 // bytes of a row of the halo'd images
@@ -1687,119 +1299,6 @@ __global__ __launch_bounds__(NT, C == 8 ? 2 : TT_NBF2_MINW4) void k_nrb_bwd_fuse
     __syncthreads();
     float* pa = part_a + (long)blockIdx.x * ADUMP;
     for (int e = tid; e < ADUMP; e += NT) pa[e] = (red[e] + red[ADUMP + e]) + (red[2 * ADUMP + e] + red[3 * ADUMP + e]);
-}
-
-// ---- data gradient and weight gradient of a narrow block in one pass (the narrow counterpart of k_wrb_dxw) --------------------
-// Phases 2a / 2b of k_nrb_bwd_fused with dA1 coming from HBM (written by k_nrb_bwd_a) instead of being computed in place: the dA1
-// and x tiles (16 x 64 pixels + halo) are staged once, dx = dy + W1^T (*) dA1 by lane-per-pixel 4x4x4 products, dW1 by transpose reads
-// of 32-byte slots (k_nrb_wgrad's scheme; the two K halves are the two halves of a row at C = 8, two consecutive rows at C = 4).
-template <int C, int D>
-__global__ __launch_bounds__(NT) void k_nrb_dxw(const e16* __restrict__ x, const e16* __restrict__ da1, const e16* __restrict__ dy,
-                                                const float* __restrict__ w1, e16* __restrict__ dx, float* __restrict__ part_w, int B,
-                                                int H, int T, int tiles_h, int tiles_t, int ntiles) {
-    using G = NTl<C, D>;
-    typedef typename VecOf<C>::type vec_t;
-    constexpr int NB = C / 4, IMG = G::NPR * 16;
-    extern __shared__ __align__(16) unsigned char smem[];
-    unsigned char* hs = smem;                                    // dA1
-    unsigned char* xs = smem + IMG;                              // x
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i4 = lane & 3;
-    const int n = lane & 15, g = lane >> 4, trj = n >> 2, trq = n & 3;
-    s16x4 A[9][NB][NB];
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-        for (int ob = 0; ob < NB; ++ob)
-#pragma unroll
-            for (int kb = 0; kb < NB; ++kb) {
-                e16x4 t4;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) t4[k] = (e16)w1[((4 * kb + k) * C + 4 * ob + i4) * 9 + (8 - tap)];
-                A[tap][ob][kb] = __builtin_bit_cast(s16x4, t4);
-            }
-    f32x4 wacc[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) wacc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const e16* zero = reinterpret_cast<const e16*>(&g_wzero16);
-    for (int v = blockIdx.x; v < ntiles; v += gridDim.x) {
-        int tile = xcd_order(v, ntiles);
-        const int tt = tile % tiles_t; tile /= tiles_t;
-        const int th = tile % tiles_h;
-        const int b = tile / tiles_h, h0 = th * G::TH, t0 = tt * G::TW;
-        const long ib = (long)b * H * T * C;
-        __syncthreads();
-        for (int i = wave * 64; i < G::NPR; i += NT) {
-            const int p = i + lane, q = p * G::PPP;
-            const int row = q / G::RW, px = q - row * G::RW;
-            const int h = h0 - D + row, t = t0 - G::DP + px;
-            const bool ok = p < G::NP && (unsigned)h < (unsigned)H && (unsigned)t < (unsigned)T;
-            const long off = ib + ((long)h * T + t) * C;
-            glds16(ok ? da1 + off : zero, hs + (long)i * 16);
-            glds16(ok ? x + off : zero, xs + (long)i * 16);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-
-        // ---- dx = dy + W1^T (*) dA1 ----
-        {
-            const int t = t0 + lane;
-            const bool valid = t < T;
-            for (int r = wave; r < G::TH; r += 4) {
-                const int h = h0 + r;
-                if (h >= H) break;
-                const long pix = ((long)b * H + h) * T + t;
-                const vec_t rq = *reinterpret_cast<const vec_t*>(dy + (valid ? pix : pix - (t - (T - 1))) * C);
-                f32x4 a4[NB];
-#pragma unroll
-                for (int ob = 0; ob < NB; ++ob) a4[ob] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int tap = 0; tap < 9; ++tap) {
-                    const int kh = tap / 3, kw = tap - 3 * kh;
-                    const int pxi = (r + kh * D) * G::RW + G::DP + lane + (kw - 1) * D;
-                    const vec_t bq = *reinterpret_cast<const vec_t*>(hs + (long)pxi * G::PXB);
-#pragma unroll
-                    for (int ob = 0; ob < NB; ++ob)
-#pragma unroll
-                        for (int kb = 0; kb < NB; ++kb) a4[ob] = mma4(A[tap][ob][kb], chunk_of<C>(bq, kb), a4[ob]);
-                }
-                vec_t o;
-#pragma unroll
-                for (int c = 0; c < C; ++c) o[c] = (e16)(a4[c >> 2][c & 3] + (float)rq[c]);
-                if (valid) *reinterpret_cast<vec_t*>(dx + pix * C) = o;
-            }
-        }
-        // ---- dW1 ----
-        {
-            constexpr int ROWB = G::RW * G::PXB;                 // bytes of an image row
-            constexpr int RPS = C == 8 ? 1 : 2;                  // rows per product step
-            constexpr int UOFF = C == 8 ? 512 : ROWB;            // byte distance of the second K half
-            const int so = 32 * (4 * g + trj) + 8 * trq;
-            for (int r = wave * RPS; r < G::TH; r += 4 * RPS) {
-                if (h0 + r >= H) break;
-                const unsigned char* gp = hs + (long)(r + D) * ROWB + G::DP * G::PXB + so;
-                const s16x4 glo = lds_tr16(gp), ghi = lds_tr16(gp + UOFF);
-                const e16x8 ga = __builtin_bit_cast(e16x8, __builtin_shufflevector(glo, ghi, 0, 1, 2, 3, 4, 5, 6, 7));
-#pragma unroll
-                for (int k = 0; k < 9; ++k) {
-                    const int kh = k / 3, kw = k - 3 * kh;
-                    const unsigned char* xp = xs + (long)(r + kh * D) * ROWB + (G::DP + (kw - 1) * D) * G::PXB + so;
-                    const s16x4 lo = lds_tr16(xp), hi = lds_tr16(xp + UOFF);
-                    wacc[k] = mma32(ga, __builtin_bit_cast(e16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7)), wacc[k]);
-                }
-            }
-        }
-    }
-    // the four waves hold the same elements: summed through LDS, ONE dump per workgroup (RedArgs::one_dump)
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) red[wave * 2304 + (k * 4 + r) * 64 + lane] = wacc[k][r];
-    __syncthreads();
-    float* pw = part_w + (long)blockIdx.x * 4 * 2304;
-    for (int i = tid; i < 2304; i += NT) pw[i] = (red[i] + red[2304 + i]) + (red[2 * 2304 + i] + red[3 * 2304 + i]);
 }
 
 // Every sum in a fixed order (bit-reproducible from run to run).  The first 9 C^2 elements are the dW1 entries (tap k, co c, ci c2),
@@ -1881,83 +1380,41 @@ template <int C, int D>
 int launch_nbwd(const e16* x, const e16* h1, const e16* dy, const float* w1, const float* w2, const float* b2,
                 e16* dx, float* dw1, float* db1, float* dw2, float* db2, unsigned char* ws, int B, int H, int T,
                 hipStream_t st, LevelCtx* ctx) {
-    const long npix = (long)B * H * T;
-    e16* da1 = reinterpret_cast<e16*>(ws);
-    float* part_a = reinterpret_cast<float*>(ws + ((npix * C * 2 + 255) / 256) * 256);
+    float* part_a = reinterpret_cast<float*>(ws);
     float* part_w = part_a + (long)MAX_A_WG * (C * C + 2 * C);
-    // Measured per launch at the bench shapes, pointwise + merged gradient kernels -> fused (with the weight image in LDS):
-    // C = 8: 0.410 / 0.409 / 0.452 -> 0.394 / 0.411 / 0.563 ms for dilation 1 / 2 / 3, C = 4: 0.40 / 0.407 / 0.408 -> 0.338 / 0.344 / 0.383 ms.
-    // Half the HBM traffic buys less than half the time because the pass is then bound by its own arithmetic (pointwise chain on the halo
-    // as well; three LDS images = 2 workgroups per CU at C = 8): fused where it wins -- C = 4 always, C = 8 at dilation 1, 2.
-    static const int fused = tt_switch("TTRAP_NARROW_FUSED16", 1);
-    if (fused) {
-        using F = NTl<C, D>;
-        constexpr int LAYOUT = 2 * ((F::NP * 16 + 63) / 64 * 64) + F::TH * F::TW * F::PXB + 11 * (C / 4) * (C / 4) * 32 + 4 * 64 * F::PXB;
-        constexpr int LDS = LAYOUT > 4 * 2304 * 4 ? LAYOUT : 4 * 2304 * 4;       // the epilogue sums the four waves' dW1 accumulators through LDS
-        const int tiles_h = (H + F::TH - 1) / F::TH, tiles_t = (T + F::TW - 1) / F::TW, ntiles = B * tiles_h * tiles_t;
-        int gf = grid_for(ntiles, LDS, 4);
-        if (gf > MAX_W_WG) gf = MAX_W_WG;
-        const FirstForm form = first_form(ctx, D, true);         // a level's first block: dx leaves gated
-        if constexpr (D == 1) {
-            if (form == FirstForm::Riding) {
-                static AttrOnce once_j;
-                auto kj = k_nrb_bwd_fused<C, D, true, true>;
-                if (int rc = raise_lds(kj, LDS, once_j)) return rc;
-                hipLaunchKernelGGL(kj, dim3(gf), dim3(NT), LDS, st, x, h1, dy, w1, w2, b2, dx, part_a, part_w, B, H, T, tiles_h, tiles_t, ntiles, ctx->skip);
-            } else if (form == FirstForm::Gated) {
-                static AttrOnce once_g;
-                auto kg = k_nrb_bwd_fused<C, D, true>;
-                if (int rc = raise_lds(kg, LDS, once_g)) return rc;
-                hipLaunchKernelGGL(kg, dim3(gf), dim3(NT), LDS, st, x, h1, dy, w1, w2, b2, dx, part_a, part_w, B, H, T, tiles_h, tiles_t, ntiles, SkipJ());
-            }
+    // Measured per launch at the bench shapes, round 4, a pointwise kernel + a merged gradient kernel (since removed) -> this one kernel (with the
+    // weight image in LDS): C = 8: 0.410 / 0.409 / 0.452 -> 0.394 / 0.411 / 0.563 ms for dilation 1 / 2 / 3, C = 4: 0.40 / 0.407 / 0.408 ->
+    // 0.338 / 0.344 / 0.383 ms.  Half the HBM traffic buys less than half the time because the pass is then bound by its own arithmetic
+    // (pointwise chain on the halo as well; three LDS images = 2 workgroups per CU at C = 8).  The round-5 cut of the kernel (above) brought
+    // C = 8 / dilation 3 to 0.323 ms: it is the backward of both widths at every dilation.
+    using F = NTl<C, D>;
+    constexpr int LAYOUT = 2 * ((F::NP * 16 + 63) / 64 * 64) + F::TH * F::TW * F::PXB + 11 * (C / 4) * (C / 4) * 32 + 4 * 64 * F::PXB;
+    constexpr int LDS = LAYOUT > 4 * 2304 * 4 ? LAYOUT : 4 * 2304 * 4;       // the epilogue sums the four waves' dW1 accumulators through LDS
+    const int tiles_h = (H + F::TH - 1) / F::TH, tiles_t = (T + F::TW - 1) / F::TW, ntiles = B * tiles_h * tiles_t;
+    int gf = grid_for(ntiles, LDS, 4);
+    if (gf > MAX_W_WG) gf = MAX_W_WG;
+    const FirstForm form = first_form(ctx, D);                   // a level's first block: dx leaves gated
+    if constexpr (D == 1) {
+        if (form == FirstForm::Riding) {
+            static AttrOnce once_j;
+            auto kj = k_nrb_bwd_fused<C, D, true, true>;
+            if (int rc = raise_lds(kj, LDS, once_j)) return rc;
+            hipLaunchKernelGGL(kj, dim3(gf), dim3(NT), LDS, st, x, h1, dy, w1, w2, b2, dx, part_a, part_w, B, H, T, tiles_h, tiles_t, ntiles, ctx->skip);
+        } else if (form == FirstForm::Gated) {
+            static AttrOnce once_g;
+            auto kg = k_nrb_bwd_fused<C, D, true>;
+            if (int rc = raise_lds(kg, LDS, once_g)) return rc;
+            hipLaunchKernelGGL(kg, dim3(gf), dim3(NT), LDS, st, x, h1, dy, w1, w2, b2, dx, part_a, part_w, B, H, T, tiles_h, tiles_t, ntiles, SkipJ());
         }
-        if (form == FirstForm::Plain) {
-            static AttrOnce once_f;
-            auto kf = k_nrb_bwd_fused<C, D, false>;
-            if (int rc = raise_lds(kf, LDS, once_f)) return rc;
-            hipLaunchKernelGGL(kf, dim3(gf), dim3(NT), LDS, st, x, h1, dy, w1, w2, b2, dx, part_a, part_w, B, H, T, tiles_h, tiles_t, ntiles, SkipJ());
-        }
-        TT_LAUNCH_CHECK();
-        RedArgs ra{part_w, gf, part_a, gf, dw1, db1, dw2, db2, 0, 1};
-        constexpr int total = 9 * C * C + C * C + 2 * C;
-        return reduce_or_defer(ctx, k_nrb_reduce<C>, total, ra, st, NREL);
     }
-    const long ngroups = (npix + 63) / 64;
-    const long want = (ngroups + 3) / 4;
-    static const int a_per_cu = tt_tune("TTRAP_BWDA_PER_CU", 4);
-    int grid = (int)(want < (long)a_per_cu * tt_cus() ? want : (long)a_per_cu * tt_cus());
-    if (grid > MAX_A_WG) grid = MAX_A_WG;
-    hipLaunchKernelGGL(k_nrb_bwd_a<C>, dim3(grid), dim3(NT), 0, st, h1, dy, w2, b2, da1, part_a, npix, ngroups);
-    TT_LAUNCH_CHECK();
-    static const int ndxw = tt_switch("TTRAP_NDXW", 1);
-    if (ndxw) {                                                  // data + weight gradient in one pass
-        using F = NTl<C, D>;
-        constexpr int LDS = 2 * F::NPR * 16 > 4 * 2304 * 4 ? 2 * F::NPR * 16 : 4 * 2304 * 4;   // images, then the four waves' accumulators
-        static AttrOnce once_x;
-        auto kx = k_nrb_dxw<C, D>;
-        if (int rc = raise_lds(kx, LDS, once_x)) return rc;
-        const int tiles_h = (H + F::TH - 1) / F::TH, tiles_t = (T + F::TW - 1) / F::TW, ntiles = B * tiles_h * tiles_t;
-        static const int x_per_cu = tt_tune("TTRAP_NDXW_PER_CU", 4);
-        int gx = grid_for(ntiles, LDS, x_per_cu);
-        if (gx > MAX_W_WG) gx = MAX_W_WG;
-        hipLaunchKernelGGL(kx, dim3(gx), dim3(NT), LDS, st, x, da1, dy, w1, dx, part_w, B, H, T, tiles_h, tiles_t, ntiles);
-        TT_LAUNCH_CHECK();
-        RedArgs ra{part_w, gx, part_a, grid, dw1, db1, dw2, db2, 0, 1};
-        constexpr int total = 9 * C * C + C * C + 2 * C;
-        return reduce_or_defer(ctx, k_nrb_reduce<C>, total, ra, st, NREL);
+    if (form == FirstForm::Plain) {
+        static AttrOnce once_f;
+        auto kf = k_nrb_bwd_fused<C, D, false>;
+        if (int rc = raise_lds(kf, LDS, once_f)) return rc;
+        hipLaunchKernelGGL(kf, dim3(gf), dim3(NT), LDS, st, x, h1, dy, w1, w2, b2, dx, part_a, part_w, B, H, T, tiles_h, tiles_t, ntiles, SkipJ());
     }
-    if (int rc = launch_nconv<C, D, 1, false>(da1, w1, nullptr, nullptr, nullptr, dy, dx, nullptr, B, H, T, st)) return rc;
-    using W = NG<C, D>;
-    static AttrOnce once_w;
-    auto kw = k_nrb_wgrad<C, D>;
-    if (int rc = raise_lds(kw, W::LDS_BYTES, once_w)) return rc;
-    const int tiles_h = (H + W::TH - 1) / W::TH, tiles_t = (T + W::TW - 1) / W::TW, ntiles = B * tiles_h * tiles_t;
-    static const int w_per_cu = tt_tune("TTRAP_NWGRAD_PER_CU", 3);
-    int gw = grid_for(ntiles, W::LDS_BYTES, w_per_cu);
-    if (gw > MAX_W_WG) gw = MAX_W_WG;
-    hipLaunchKernelGGL(kw, dim3(gw), dim3(NT), W::LDS_BYTES, st, x, da1, part_w, B, H, T, tiles_h, tiles_t, ntiles);
     TT_LAUNCH_CHECK();
-    RedArgs ra{part_w, gw, part_a, grid, dw1, db1, dw2, db2};
+    RedArgs ra{part_w, gf, part_a, gf, dw1, db1, dw2, db2, 0, 1};
     constexpr int total = 9 * C * C + C * C + 2 * C;
     return reduce_or_defer(ctx, k_nrb_reduce<C>, total, ra, st, NREL);
 }
@@ -1996,8 +1453,7 @@ inline bool shape_ok(int B, int C, int H, int T) {
 }
 
 // dx *= ELU'(x) in place, 8 elements per thread step: what tt_wide_level_bwd_gated runs behind a first block whose backward kernel has no
-// gated form (a dilation other than 1, the A/B paths behind TTRAP_DXW / TTRAP_NARROW_FUSED16 / TTRAP_WBWD1): first_form
-// (wide_common.h) is then not asked or answers Plain, and the level's LevelCtx::gated stays false
+// gated form (a dilation other than 1): first_form (wide_common.h) then answers Plain, and the level's LevelCtx::gated stays false
 __global__ __launch_bounds__(256) void k_gate_dx(e16* __restrict__ dx, const e16* __restrict__ x, long n8) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
         e16x8 d = reinterpret_cast<const e16x8*>(dx)[i];
@@ -2014,9 +1470,12 @@ extern "C" {
 
 int64_t tt_wide_scratch_bytes(int B, int C, int H, int T) {
     if (!shape_ok(B, C, H, T)) return -1;
+    // C = 4, 8 (launch_nbwd) and C = 16 (the strips) keep dA1 in LDS: the kernels' dumps only; C = 32 (launch_bwd): dA1 in front of them
+    if (C == 4) return ndump_floats<4>() * 4;
+    if (C == 8) return ndump_floats<8>() * 4;
+    if (C == 16) return tt_wide_onepass_scratch_bytes(16);
     const long npix = (long)B * H * T;
-    const long dumps = C == 4 ? ndump_floats<4>() : C == 8 ? ndump_floats<8>() : C == 16 ? dump_floats<16>() : dump_floats<32>();
-    return ((npix * C * 2 + 255) / 256) * 256 + dumps * 4;
+    return ((npix * C * 2 + 255) / 256) * 256 + dump_floats<32>() * 4;
 }
 
 int tt_wide_pack(const float* x, void* out, int B, int C, int H, int T, void* stream) {
@@ -2108,7 +1567,7 @@ int tt_wide_bwd_kernel_attr(int kernel, int C, int dilation, int form, int* loca
     if (!local_bytes || !num_regs || form < 0 || form > 2) return TT_E_BADARG;
     if (kernel == TT_BWD_KERNEL_STRIPS) return ttx_wide_bwds_attr(C, dilation, form, local_bytes, num_regs);
 #define TT_KA(F, CC, DD) if (C == CC && dilation == DD) return F<CC, DD>(form, local_bytes, num_regs)
-    if (kernel == TT_BWD_KERNEL_DXW) { TT_KA(dxw_attr, 16, 1); TT_KA(dxw_attr, 16, 2); TT_KA(dxw_attr, 16, 3); TT_KA(dxw_attr, 32, 1); TT_KA(dxw_attr, 32, 2); TT_KA(dxw_attr, 32, 3); }
+    if (kernel == TT_BWD_KERNEL_DXW) { TT_KA(dxw_attr, 32, 1); TT_KA(dxw_attr, 32, 2); TT_KA(dxw_attr, 32, 3); }
     if (kernel == TT_BWD_KERNEL_NARROW) { TT_KA(nbf_attr, 4, 1); TT_KA(nbf_attr, 4, 2); TT_KA(nbf_attr, 4, 3); TT_KA(nbf_attr, 8, 1); TT_KA(nbf_attr, 8, 2); TT_KA(nbf_attr, 8, 3); }
 #undef TT_KA
     return TT_E_UNSUPPORTED;
@@ -2142,8 +1601,9 @@ int64_t tt_wide_level_scratch_bytes(int nblocks, int B, int C, int H, int T) {
     return one < 0 || nblocks < 1 || nblocks > 4 ? -1 : (int64_t)nblocks * ((one + 255) / 256 * 256);
 }
 
-// The level's backward: gate = leave dx * ELU'(x); skip.g = the skip-join backward to ride on the first block.  Returns TT_W_JOIN_LEFT when
-// that block took a kernel without the riding form (an A/B dispatch; C = 32 on the one-pass path).
+// The level's backward: gate = leave dx * ELU'(x); skip.g = the skip-join backward to ride on the first block (at dilation 1, which
+// tt_wide_level_bwd_gated_join checks: every width's launcher has the riding form there -- C = 4, 8 launch_nbwd, C = 16 the strips, C = 32
+// launch_dxw -- and first_form (wide_common.h) answers nothing else while skip.g is set, so a join is taken or the block's call fails).
 static int level_bwd(int gate, const SkipJ& skip, int nblocks, const void* const* x, const void* const* h1, const void* dy, const float* const* w1,
                      const float* const* w2, const float* const* b2, void* dx, void* tmp0, void* tmp1, float* const* dw1,
                      float* const* db1, float* const* dw2, float* const* db2, void* ws, int B, int C, int H, int T,
@@ -2197,7 +1657,7 @@ static int level_bwd(int gate, const SkipJ& skip, int nblocks, const void* const
         }
         TT_LAUNCH_CHECK();
     }
-    return skip.g && !ctx.joined ? TT_W_JOIN_LEFT : 0;
+    return 0;
 }
 
 int tt_gate16(void* g, const void* y, int64_t n, void* stream) {

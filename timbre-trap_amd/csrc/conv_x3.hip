@@ -1517,7 +1517,7 @@ __global__ __launch_bounds__(NT) void k_x3_bwd_a(const e16* __restrict__ h1, con
 }
 
 // ---- 3x3 weight gradient: dW1[co][ci][tap] = sum_pix g1[co][pix] x[ci][pix + tap], K = pixels, 32 per product -------------------------
-// The split-operand form of k_wrb_wgrad (conv_wide_bf16.hip).  The x tile (with halo) and the g1 tile are x3 LDS images filled by LDS-DMA
+// Both operands split (hi + lo planes).  The x tile (with halo) and the g1 tile are x3 LDS images filled by LDS-DMA
 // ([pixel][hi C][lo C]); all four operand planes come out of them by transpose reads (two per operand: pixels 4g..4g+3 and 16+4g..16+4g+3 of
 // the 32-pixel chunk -- the K order is free as long as both operands use the same one).  At C = 32 (128 bytes per pixel) the two 16-channel
 // halves of either plane are swapped in every second PAIR of pixels (a permutation of the DMA sources), which keeps the four pixels a

@@ -179,7 +179,6 @@ struct LevelCtx {
     bool gate = false;             // the block being called is the level's first and should leave dx * ELU'(x)
     SkipJ skip;                    // the skip-join backward that may ride on that block's epilogue (.g == nullptr: none)
     bool gated = false;            // out: the first block's kernel gated dx (otherwise k_gate_dx runs behind the level)
-    bool joined = false;           // out: ... and took the join (otherwise TT_W_JOIN_LEFT)
 };
 int ttx_wide_wprep_batch(int C, int n, const float* const* w1, const float* const* w2, void* const* ws, hipStream_t st);
 // tt_wide_rb_bwd_onepass with the calling level's context (nullptr: the public call)
@@ -216,15 +215,14 @@ __device__ __forceinline__ void skipj_finish(float dot, const SkipJ& sj) {
 }
 
 // Which form of its kernel a block backward launches: the gated and riding forms exist for a level's first block at dilation 1 only (the
-// reference's levels start there), the riding form not in every launcher.  Notes the choice in the context: that is how the level learns
-// whether the gate and the join are still to be done.
+// reference's levels start there).  Notes in the context that dx leaves gated: that is how the level learns whether the gate is still to
+// be done.  A join that was asked for is never answered with Gated: a launcher without the riding form (the C = 32 strips, which no level
+// dispatches to) fails its call instead of dropping the join.
 enum class FirstForm { Plain, Gated, Riding };
-inline FirstForm first_form(LevelCtx* ctx, int D, bool has_riding) {
+inline FirstForm first_form(LevelCtx* ctx, int D) {
     if (!ctx || !ctx->gate || D != 1) return FirstForm::Plain;
     ctx->gated = true;
-    if (!has_riding || !ctx->skip.g) return FirstForm::Gated;
-    ctx->joined = true;
-    return FirstForm::Riding;
+    return ctx->skip.g ? FirstForm::Riding : FirstForm::Gated;
 }
 
 // Where a launcher starts its reduce: now, or -- inside tt_wide_level_bwd -- into the level's batch

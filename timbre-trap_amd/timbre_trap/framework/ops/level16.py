@@ -97,11 +97,8 @@ def _level16_backward(ctx, dy):
             if ride is not None:
                 # one parked skip-join backward on this level's input: it rides on the first block's gated epilogue (tt_wide_level_bwd_gated_join)
                 pg, pe, pw, pidx, preps, pds = ride
-                rc = lib.tt_wide_level_bwd_gated_join(*args, ptr(pg), preps, ptr(pw), pidx, ptr(pds), st)
-                if rc == 0:
-                    ctx.link.pending = []
-                elif rc != 1:                                    # 1 = TT_W_JOIN_LEFT: the level is done, the join is left to flush_pending below
-                    check(rc, 'tt_wide_level_bwd_gated_join')
+                check(lib.tt_wide_level_bwd_gated_join(*args, ptr(pg), preps, ptr(pw), pidx, ptr(pds), st), 'tt_wide_level_bwd_gated_join')
+                ctx.link.pending = []
             else:
                 check(fn(*args, st), 'tt_wide_level_bwd')
         _skip.flush_pending(ctx.link, dx)
