@@ -690,6 +690,36 @@ int tt_pitch_targets(const int* idx, const int64_t* tracks, int n_tracks, const 
                      const int* bins, const unsigned char* lost, const double* weights, int radius, int F, int out_float32, void* scratch,
                      void* out, int* flags, void* stream);
 
+/* ---- the FiLM layer of TimbreTrapFiLM (csrc/film.hip; version 17) ---------------------------------------------------------------------
+ * Replaces FiLM.forward (timbre_trap/framework/modules.py:847-889: `y = x * self.gamma(condition) + self.beta(condition)` between two
+ * transposes) as TimbreTrapFiLM.decode calls it (modules.py:814-844) and its autograd backward, for latents x (B, D, T) fp32 with T
+ * contiguous, gamma / beta = nn.Linear(2, D) (gw, bw: (D, 2); gb, bb: (D)) and R = 1 or 2 conditions c_r = (c_r0, c_r1) given in HOST
+ * memory (cond, R x 2 floats, read at launch and passed to the kernels by value):
+ *     G_r[d] = fl(fl(fl(gw[d][0] c_r0) + fl(gw[d][1] c_r1)) + gb[d]),   Bt_r[d] the same from bw, bb   (for a one-hot condition: the
+ *     bits of nn.Linear)
+ * Every product and every sum is rounded on its own, nothing is contracted into a fused multiply-add: the reference's bits.  Any
+ * B, D, T >= 1; element offsets are 64-bit; rows are read 16 bytes at a time where T % 4 == 0 and the tensors are 16-byte aligned and
+ * element by element otherwise, with the same results bit for bit.  No atomics: results are bit-reproducible.  The launch functions
+ * neither allocate nor synchronise.
+ *   tt_film_tile_frames    (modules.py:883) frames of one (clip, channel) row that one workgroup covers: the T at which the kernels'
+ *                          index arithmetic changes
+ *   tt_film_scratch_bytes  (modules.py:883) bytes of `ws` for tt_film_bwd with parameter gradients
+ *   tt_film_fwd            (modules.py:880-887) y[r B + b][d][t] = fl(fl(x[b][d][t] G_r[d]) + Bt_r[d]); y: (R B, D, T).  R = 2 is the
+ *                          pair form (reconstruction and transcription of the same latents): one read of x, two halves written
+ *   tt_film_bwd            (autograd of modules.py:883) dy: (R B, D, T).  dx (B, D, T), written unless NULL: fl(G_0 dy_0), for R = 2
+ *                          fl(fl(G_0 dy_0) + fl(G_1 dy_1)) -- autograd's sum of the two branches.  dgw, dgb, dbw, dbb: all four or all
+ *                          NULL; ACCUMULATED (+=) from P_r[d] = sum_{b,t} x dy_r and S_r[d] = sum_{b,t} dy_r:
+ *                              dgw[d][j] += sum_r c_rj P_r,  dgb[d] += sum_r P_r,  dbw[d][j] += sum_r c_rj S_r,  dbb[d] += sum_r S_r
+ *                          P_r and S_r: per workgroup at most four fp32 terms in a row, then pairwise; the workgroups' partial sums go
+ *                          through ws and a second launch adds them in float64 in a fixed order.  x and ws may be NULL without
+ *                          parameter gradients. */
+int     tt_film_tile_frames(void);
+int64_t tt_film_scratch_bytes(int B, int D, int T, int R);
+int tt_film_fwd(const float* x, const float* gw, const float* gb, const float* bw, const float* bb, const float* cond, float* y,
+                int B, int D, int T, int R, void* stream);
+int tt_film_bwd(const float* x, const float* dy, const float* gw, const float* gb, const float* cond, float* dx, float* dgw, float* dgb,
+                float* dbw, float* dbb, void* ws, int B, int D, int T, int R, void* stream);
+
 /* ---- track audio: mono mix, sample-rate conversion, inf-norm (csrc/resample.hip; version 12) ----------------------------------------
  * Replaces the three lines of AudioDataset.get_audio (timbre_trap/datasets/AudioDataset.py:69-77) that stand between a decoded file
  * and the CQT -- `torch.mean(audio, dim=0, keepdim=True)`, `torchaudio.functional.resample(audio, fs, self.sample_rate)`,

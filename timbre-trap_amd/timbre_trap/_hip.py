@@ -35,7 +35,9 @@ SOURCES = ['cqt.hip', 'cqt_generic.hip', 'conv_generic.hip', 'conv_mfma.hip', 'c
            # note annotations to frame ranges and per-frame note lists (NoteDataset.notes_to_multi_pitch)
            'notes.hip',
            # frame-level pitch annotations to batched targets (PitchDataset.resample_multi_pitch + multi_pitch_to_activations)
-           'pitch.hip']
+           'pitch.hip',
+           # the FiLM layer of TimbreTrapFiLM: per-channel affine map of the latents, forward (single and pair form) and backward
+           'film.hip']
 
 _lib = None
 
@@ -195,6 +197,10 @@ _PROTOS = {
     'tt_pitch_scratch_bytes': (c_int64, [I, I]),
     'tt_pitch_nearest': (c_int, [P, P, I, P, P, I, I, P, P]),
     'tt_pitch_targets': (c_int, [P, P, I, P, I, I, P, P, P, P, I, I, I, P, P, P, P]),
+    'tt_film_tile_frames': (c_int, []),
+    'tt_film_scratch_bytes': (c_int64, [I, I, I, I]),
+    'tt_film_fwd': (c_int, [P, P, P, P, P, P, P, I, I, I, I, P]),
+    'tt_film_bwd': (c_int, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
     'tt_resample_tile': (c_int, []),
     'tt_resample_direct_tile': (c_int, []),
     'tt_resample_max_taps': (c_int, []),

@@ -403,20 +403,46 @@ class TimbreTrap(nn.Module):
         return reconstruction, latents, transcription, transcription_rec, transcription_scr, losses
 
 
-class _OutOfScopeVariant(TimbreTrap):
+class TimbreTrapFiLM(TimbreTrap):
     """
-    The FiLM ablation variant of the reference (modules.py:780-889) is outside the accelerated hot path (a condition-dependent affine
-    map in front of the latent head).  The names exist so that ``isinstance`` checks in experiments/train.py:406-411
-    keep working; constructing one raises.
+    FiLM variant (reference modules.py:780-844): the decoder is switched between reconstruction and transcription by a per-channel affine
+    map of the latents, y = x * gamma(c) + beta(c) with c = (transcribe, not transcribe), instead of a constant extra latent channel;
+    ``Decoder.convin`` takes ``latent_size`` channels.  The map is one streaming kernel each way (csrc/film.hip, ops.FilmFn) on the fp32
+    latents of every route; everything behind it -- latent head, levels, skip joins, pair decode over 2 B clips -- is TimbreTrap's.
+    ``latent_size`` must be given: the reference itself cannot construct this model without one (modules.py:799 reads ``in_channels`` of
+    an nn.Sequential), so no checkpoint of such a model exists.
     """
 
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError('%s is an ablation variant that the MI355X path does not implement'
-                                  % type(self).__name__)
+    def __init__(self, sample_rate, n_octaves, bins_per_octave, secs_per_block=3,
+                 latent_size=None, model_complexity=1, skip_connections=False):
+        if latent_size is None:
+            raise NotImplementedError('TimbreTrapFiLM needs an explicit latent_size: with latent_size=None the reference raises while it '
+                                      'constructs the model (modules.py:799), so there is nothing to be compatible with')
+        TimbreTrap.__init__(self, sample_rate, n_octaves, bins_per_octave, secs_per_block,
+                            latent_size, model_complexity, skip_connections)
+        # in the reference's order (the default initialisation draws from the RNG in this order)
+        convin_out_channels = self.decoder.convin[0].out_channels
+        convin_kernel_size = self.decoder.convin[0].kernel_size
+        self.decoder.convin = nn.Sequential(
+            nn.ConvTranspose2d(latent_size, convin_out_channels, kernel_size=convin_kernel_size),
+            nn.ELU(inplace=True))
+        self.film_layer = FiLM(latent_size, n_conditions=2)
 
+    def decode(self, latents, embeddings=None, transcribe=False):
+        """latents (B,D,T) -> logits (B,2,F,T); the condition is the one-hot pair (transcribe, not transcribe)."""
+        z = self.film_layer(latents, (float(bool(transcribe)), float(not transcribe)))
+        return self.decoder(z, embeddings, indicator=None, act=self.OUT_ACT)
 
-class TimbreTrapFiLM(_OutOfScopeVariant):
-    pass
+    def decode_pair(self, latents, embeddings=None):
+        """(decode(latents, embeddings), decode(latents, embeddings, True)).  Where TimbreTrap.decode_pair runs the decoder once over 2 B
+        clips, so does this: the pair form of the FiLM kernel reads the latents once and writes the modulated reconstruction half and
+        transcription half back to back -- no concatenated copies."""
+        joins = embeddings is not None and all(isinstance(e, ops.SkipJoin) and ops.is_cl16(e.e) for e in embeddings)
+        if self.PAIR_DECODE and (embeddings is None or joins) and ops.cl16_mode() and torch.is_grad_enabled() and latents.dim() == 3:
+            f = self.film_layer
+            z2 = ops.film_modulate(latents, f.gamma.weight, f.gamma.bias, f.beta.weight, f.beta.bias, (0.0, 1.0, 1.0, 0.0), reps=2)
+            return self.decoder(z2, embeddings, indicator=None, pair=True, act=self.OUT_ACT)
+        return self.decode(latents, embeddings), self.decode(latents, embeddings, True)
 
 
 class TimbreTrapMag(TimbreTrap):
@@ -473,5 +499,24 @@ class TimbreTrapMagDB(TimbreTrapMag):
 
 
 class FiLM(nn.Module):
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError('FiLM belongs to an ablation variant that the MI355X path does not implement')
+    """
+    FiLM conditioning layer (reference modules.py:847-889): y = x * gamma(condition) + beta(condition) per channel of x (..., D, T), with
+    gamma and beta nn.Linear(n_conditions, D) -- kept as PARAMETER CONTAINERS (the reference's keys, default initialisation and RNG
+    order); the map itself is csrc/film.hip.  Two conditions only: the kernels serve the model's reconstruction / transcription switch.
+    """
+
+    def __init__(self, embedding_size, n_conditions):
+        if n_conditions != 2:
+            raise NotImplementedError('FiLM with %r conditions: the MI355X path implements the two-condition switch of TimbreTrapFiLM'
+                                      % (n_conditions,))
+        nn.Module.__init__(self)
+        self.gamma = nn.Linear(n_conditions, embedding_size)
+        self.beta = nn.Linear(n_conditions, embedding_size)
+
+    def forward(self, x, condition):
+        """x (..., D, T); condition: two values, as a host sequence or a tensor.  The kernel takes the condition BY VALUE: a host sequence
+        or CPU tensor costs nothing, a device tensor is read back with one ``.tolist()`` -- a host synchronisation (TimbreTrapFiLM's own
+        decode never passes one)."""
+        if torch.is_tensor(condition):
+            condition = condition.detach().reshape(-1).tolist()
+        return ops.film_modulate(x, self.gamma.weight, self.gamma.bias, self.beta.weight, self.beta.bias, condition)

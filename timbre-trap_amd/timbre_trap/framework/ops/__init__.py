@@ -2,7 +2,7 @@
 torch.autograd bindings of the gfx950 kernels (C ABI: include/ttrap.h) and the routing in front of them.  Which switches exist: the block
 right below.  Which kernel a call takes: the routing functions at the end of this file (what modules.py / objectives.py / cqtwrapper.py
 call).  What a binding does: the family modules -- fp32 (channel-planar), cl16 / level16 / skip (16-bit channels-last), x3 (split-operand
-inference), losses.  Every Function owns a forward and a hand-written backward that call straight into libttrap_hip.so on the current HIP
+inference), losses, film (the FiLM layer of TimbreTrapFiLM).  Every Function owns a forward and a hand-written backward that call straight into libttrap_hip.so on the current HIP
 stream; torch only allocates the tensors.  Nothing here has a CPU path -- tensors must live on the GPU.
 """
 
@@ -130,6 +130,7 @@ from .x3 import (X3LevelTrainFn, _x3_blocks_ok, _x3_size_ok, from_x3, is_x3, x3_
                  x3_latent_decode, x3_latent_encode, x3_latent_ok, x3_level, x3_level_train, x3_range_ok, x3_strided_conv, x3_training,
                  x3_transposed_conv, x3_vouched, x3_vouched_scope, x3n_level)
 from .losses import Activations1Fn, ActivationsFn, SqDiff2Fn, SqDiffLossFn, TranscriptionLossFn, decibels, magnitude  # noqa: E402,F401
+from .film import FilmFn, film_modulate  # noqa: E402,F401
 
 
 # ---- routing: which kernel a call takes ---------------------------------------------------------------------------------------------------
