@@ -690,6 +690,40 @@ int tt_pitch_targets(const int* idx, const int64_t* tracks, int n_tracks, const 
                      const int* bins, const unsigned char* lost, const double* weights, int radius, int F, int out_float32, void* scratch,
                      void* out, int* flags, void* stream);
 
+/* ---- random stem mixtures for training batches (csrc/mix.hip; version 18) -------------------------------------------------------------
+ * Replaces, per item of a StemMixingDataset (timbre_trap/datasets/BaseDataset.py:272-332), the device-shaped work behind its random
+ * draws: the excerpt cut of every stem (AudioDataset.slice_audio, AudioDataset.py:113-141), the sums of the stems' audio
+ * (BaseDataset.py:307-320) and the sum and clamp of the annotated stems' target maps (BaseDataset.py:323), for a whole batch in one
+ * launch each, from audio that stays on the device:
+ *     arena    fp32, the samples of every track, concatenated
+ *     tracks   int64 [n_tracks][2] = {base, length}: track n's samples are arena[base .. base + length)
+ * All pointers are device pointers.  Nothing here uses atomics, scratch or a work buffer; offsets are 64-bit; every output element is
+ * one chain of additions in stem order, so no result depends on the launch geometry and two runs agree bit for bit.  The order is that
+ * of an explicit loop over the stems from +0, which is what torch.sum(dim=0) on the CPU gives for up to 4 stems, and for 5 outside the
+ * last few elements of a row (tests/test_mix_restatement.py); the sign of a zero is not part of the contract.
+ *   tt_mix_tile          (AudioDataset.py:113-141) output samples per workgroup of tt_mix_audio: the N at which its index arithmetic
+ *                        changes
+ *   tt_mix_targets_tile  (BaseDataset.py:323) output elements of one item's F T that one workgroup of tt_mix_targets covers
+ *   tt_mix_audio    (AudioDataset.py:113-141; BaseDataset.py:307-320) y (B, N).  Item b's stems are item_off[b] .. item_off[b + 1]
+ *                   (item_off: B + 1 ints, non-decreasing from 0); the first item_split[b] of them are its audio-only group, the rest
+ *                   its annotated group (the order separate_ground_truth leaves, utils/data.py:183-195).  Sample i of stem s is
+ *                   arena[base + stem_start[s] + i] of track stem_track[s] where 0 <= stem_start[s] + i < length and +0 elsewhere:
+ *                   stem_start >= 0 is slice_audio's slice (AudioDataset.py:113-125), stem_start = -pad_left its zero padding
+ *                   (:126-141).  y[b] = (sum of the audio-only group) + (sum of the annotated group), each added in fp32 in stem
+ *                   order (BaseDataset.py:309, 313, 320); an item without stems is zeros; one stem per item is an excerpt batch.
+ *                   Track ids are the caller's to check on the host, where the tables are made (utils/mixing.py raises IndexError):
+ *                   the entry sees device pointers only, and a stem whose id is outside [0, n_tracks) reads as silence.
+ *                   TT_E_BADARG for a negative size or a missing pointer
+ *   tt_mix_targets  (BaseDataset.py:323; train.py:394) maps float64 (S, F, T), the annotated stems' targets in stem order; item_off
+ *                   B + 1 ints into them.  out[b] (F, T) = clamp(maps[item_off[b]] + maps[item_off[b] + 1] + ..., 0, 1), added in
+ *                   float64 in stem order, as float64 or (out_float32 != 0) rounded once to float32; a NaN stays a NaN as in
+ *                   torch.clamp; an item without a map is zeros (maps may be NULL when there is none at all).  Any F, T >= 0 */
+int tt_mix_tile(void);
+int tt_mix_targets_tile(void);
+int tt_mix_audio(const float* arena, const int64_t* tracks, int n_tracks, const int* stem_track, const int64_t* stem_start,
+                 const int* item_off, const int* item_split, int B, int64_t N, float* y, void* stream);
+int tt_mix_targets(const double* maps, const int* item_off, int B, int F, int64_t T, int out_float32, void* out, void* stream);
+
 /* ---- the FiLM layer of TimbreTrapFiLM (csrc/film.hip; version 17) ---------------------------------------------------------------------
  * Replaces FiLM.forward (timbre_trap/framework/modules.py:847-889: `y = x * self.gamma(condition) + self.beta(condition)` between two
  * transposes) as TimbreTrapFiLM.decode calls it (modules.py:814-844) and its autograd backward, for latents x (B, D, T) fp32 with T

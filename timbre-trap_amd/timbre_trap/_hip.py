@@ -37,7 +37,10 @@ SOURCES = ['cqt.hip', 'cqt_generic.hip', 'conv_generic.hip', 'conv_mfma.hip', 'c
            # frame-level pitch annotations to batched targets (PitchDataset.resample_multi_pitch + multi_pitch_to_activations)
            'pitch.hip',
            # the FiLM layer of TimbreTrapFiLM: per-channel affine map of the latents, forward (single and pair form) and backward
-           'film.hip']
+           'film.hip',
+           # random stem mixtures of a training batch: excerpt gather-and-sum of the audio, segmented sum-and-clamp of the target maps
+           # (StemMixingDataset.__getitem__)
+           'mix.hip']
 
 _lib = None
 
@@ -201,6 +204,10 @@ _PROTOS = {
     'tt_film_scratch_bytes': (c_int64, [I, I, I, I]),
     'tt_film_fwd': (c_int, [P, P, P, P, P, P, P, I, I, I, I, P]),
     'tt_film_bwd': (c_int, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
+    'tt_mix_tile': (c_int, []),
+    'tt_mix_targets_tile': (c_int, []),
+    'tt_mix_audio': (c_int, [P, P, I, P, P, P, P, I, L, P, P]),
+    'tt_mix_targets': (c_int, [P, P, I, I, L, I, P, P]),
     'tt_resample_tile': (c_int, []),
     'tt_resample_direct_tile': (c_int, []),
     'tt_resample_max_taps': (c_int, []),

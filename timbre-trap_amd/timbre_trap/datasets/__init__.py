@@ -59,3 +59,6 @@ except Exception as _e:                          # no reference on the path, or 
         """
 
         prepare_audio = staticmethod(prepare_audio)
+
+    # the mixing wrapper's stand-in: the same draws, whole batches formed on the device (utils/mixing.py)
+    from ..utils.mixing import AudioBank, StemMixer, StemSource

@@ -26,6 +26,7 @@ from .metrics import (MultipitchEvaluator, multipitch_metrics, multipitch_metric
                       signal_distortion_ratio, signal_distortion_ratio_device, SignalDistortionRatio)
 from .notes import notes_to_multi_pitch, notes_csr_device, notes_to_activations, note_tiles
 from .pitch import PitchBank, pitch_to_activations, pitch_tiles
+from .mixing import AudioBank, StemSource, StemMixer, mix_tiles, mix_targets
 from .audio import sinc_resample_kernel, resample_host, resample, mix_resample, prepare_audio
 from .trainloop import (make_schedulers, checkpoints_for, StepLogger, TrainingState, save_checkpoint, print_and_log,
                         log_gradient_norms, TRAIN_TAGS)
