@@ -70,6 +70,18 @@ __device__ __forceinline__ f32x4 mma16(s16x4 a, s16x4 b, f32x4 c) { return __bui
 __device__ __forceinline__ f32x4 mma4(s16x4 a, s16x4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(a, b, c, 0, 0, 0); }
 #endif
 
+// Two floats to one 32-bit word of two 16-bit elements (lo in bits 0-15), round to nearest even: ONE packed conversion.  Where a kernel
+// needs the same rounded values both as a matrix operand and as a row it stores, the element-wise casts come out of the compiler as one
+// conversion per element plus a v_perm_b32 for the operand AND a packed conversion for the store (bf16); a word made here serves both.
+// A two-element vector conversion, not an asm statement: the compiler pads the wait states between a matrix product and the vector
+// instructions around it only for instructions it knows, and v_cvt_pk_bf16_f32 in asm statements between the 4 x 4 x 4 products of the
+// narrow backward's chain gave values that differed from call to call.
+__device__ __forceinline__ unsigned pack2_e16(float lo, float hi) {
+    typedef float f32x2_ __attribute__((ext_vector_type(2)));
+    typedef e16 e16x2_ __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_{lo, hi}), e16x2_));      // v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32
+}
+
 __device__ __forceinline__ int xcd_order(int v, int n) {          // see conv_mfma.hip: one contiguous eighth of the raster per XCD
     const int per = n >> 3;
     return v < (per << 3) ? (v & 7) * per + (v >> 3) : v;

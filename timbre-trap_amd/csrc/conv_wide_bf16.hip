@@ -956,7 +956,17 @@ __global__ __launch_bounds__(NT, C == 8 ? 3 : 1) void k_nrb_conv(const e16* __re
 // (ii)  x is not needed before phase 2b: its DMA is issued last and waited for only behind phase 1 (s_waitcnt vmcnt(NITX) in front);
 // (iii) phase 1's per-step index arithmetic (flat pixel -> row / column by division, six compares for "this tile's own pixel") is
 //       tile-independent: LDS offset and a packed (row, column) key are computed once per kernel, the tile contributes two scalars;
-// (iv)  one conversion of dA2 to 16 bits serves the matrix operand and the dW2 staging buffer (the compiler emitted both forms).
+// (iv)  one conversion of dA2 to 16 bits serves the matrix operand and the dW2 staging buffer.  Written element by element the compiler
+//       still emitted both forms and a third (per channel pair two single conversions and a v_perm_b32 for the operand, one packed
+//       conversion for the buffer); since the pairs are made as 32-bit words (pack2_e16, bf16_common.h) and only the words are used, a
+//       phase-1 step holds C packed conversions -- C / 2 for dA2, C / 2 for dA1 -- and no permute.
+// Since then, from the compiled loops (profiles/narrow_bwd_valu_isa.txt, A/B in profiles/narrow_bwd_valu_ab.txt):
+// (v)   the steps of phase 1 without a pixel of the tile proper (2-7 of the 19-25 chunks of 64 pixels, fixed by C and the dilation) run the
+//       chain and the dA1 store only: no sums, no dW2 row, no transpose reads, no 16-row product of an all-zero operand.
+// (Measured with these and dropped, each against the kernel without it, profiles/narrow_bwd_valu_ab.txt section 4: b2, the C operand of the
+// chain's first products, held in vector registers across the tile loop instead of four moves per step from its scalar copies -- the six
+// kernels of the train step +0.7 % in sum; interior tiles staged with the request's scalar-base form and M0 by scalar arithmetic instead
+// of a 64-bit vector add and a v_readfirstlane_b32 per request, 40 vector instructions per tile less -- +1.0 % in sum.)
 // (Round 5, measured and dropped at C = 8: three workgroups per CU instead of two -- data-gradient weights read per tap from the LDS image instead
 // of held in 72 registers (142-157 registers), tiles of 12 / 12 / 8 rows so that three sets of images fit: 51.59 / 51.39 ms per step against
 // 51.64 / 51.21; 8-row tiles throughout: 52.16 / 51.94.  profiles/r05_nbf2_c8_occupancy_ab.txt)
@@ -989,7 +999,9 @@ __global__ __launch_bounds__(NT, C == 8 ? 2 : TT_NBF2_MINW4) void k_nrb_bwd_fuse
     unsigned char* gs = smem + IMG;                              // dy             (halo'd)
     unsigned char* xs = smem + 2 * IMG;                          // x              (the tile's own pixels)
     unsigned char* wimg = xs + XIMG;                             // A operands of every phase, 16-bit
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i4 = lane & 3;
+    // the wave index as a SCALAR: which steps of phase 1 a wave runs in full is a scalar compare and branch, and the row loops of phase 2
+    // count in scalar registers (the plain and gated C = 4 forms stay inside their 128 registers without private memory only so)
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), i4 = lane & 3;
     const int n = lane & 15, g = lane >> 4, trj = n >> 2, trq = n & 3;
 
     float b2r[C], acc[2 * C];                                    // db1 | db2
@@ -1003,9 +1015,8 @@ __global__ __launch_bounds__(NT, C == 8 ? 2 : TT_NBF2_MINW4) void k_nrb_bwd_fuse
     f32x4 dw2m = f32x4{0.f, 0.f, 0.f, 0.f};
     const e16* zero = reinterpret_cast<const e16*>(&g_wzero16);
     unsigned char* abuf = wimg + 11 * NB * NB * 32 + wave * (64 * G::PXB);      // this wave's 64 pixels of masked dA2
-    vec_t zero_px;
-#pragma unroll
-    for (int c = 0; c < C; ++c) zero_px[c] = (e16)0.f;
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    typedef unsigned u32xh __attribute__((ext_vector_type(C / 2)));             // a pixel's channels as 32-bit words
     for (int e = tid; e < (2 + 9) * NB * NB * 4; e += NT) {
         const int l4 = e & 3, kb = (e >> 2) % NB, ob = (e >> 2) / NB % NB, m = (e >> 2) / (NB * NB);
         e16x4 a;
@@ -1060,6 +1071,10 @@ __global__ __launch_bounds__(NT, C == 8 ? 2 : TT_NBF2_MINW4) void k_nrb_bwd_fuse
         const long ib = (long)b * H * T * C;
         // every wave is done READING the three images of the previous tile (its dx stores may still be in flight: they touch no LDS)
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        // the wave index again, opaque per tile: the bounds of phase 1's steps are then one scalar instruction where they are used; seen
+        // through, all of them are hoisted out of the tile loop and kept, and the scalar registers spill into vector lanes
+        int wv = wave;
+        asm volatile("" : "+s"(wv));
         const bool fast = h0 >= D && h0 + G::TH + D <= H && t0 >= G::DP && t0 + G::TW + G::DP <= T;
         if (fast) {
             const long first = ib + ((long)(h0 - D) * T + (t0 - G::DP)) * C;
@@ -1068,14 +1083,16 @@ __global__ __launch_bounds__(NT, C == 8 ? 2 : TT_NBF2_MINW4) void k_nrb_bwd_fuse
             const char* xb = reinterpret_cast<const char*>(x + ib + ((long)h0 * T + t0) * C);
 #pragma unroll
             for (int it = 0; it < NITD; ++it) {
-                const int i = wave * 64 + it * NT;
+                // (the LDS destination from the VECTOR form of the wave index, read back per request: from the scalar one, with the requests in
+                // their scalar-base form, these kernels were no faster -- the note in front of the kernel)
+                const int i = (tid >> 6) * 64 + it * NT;
                 if (it + 1 < NITD || i + lane < G::NP) {         // (only the last round has lanes past the image)
                     glds16_h1(hb + rel[it], hs + (long)i * 16);
                     glds16(gb + rel[it], gs + (long)i * 16);
                 }
             }
 #pragma unroll
-            for (int it = 0; it < NITX; ++it) glds16_x(xb + relx[it], xs + (long)(wave * 64 + it * NT) * 16);
+            for (int it = 0; it < NITX; ++it) glds16_x(xb + relx[it], xs + (long)((tid >> 6) * 64 + it * NT) * 16);
         } else {
             for (int i = wave * 64; i < G::NPR; i += NT) {
                 const int p = i + lane, q = p * G::PPP;
@@ -1112,20 +1129,20 @@ __global__ __launch_bounds__(NT, C == 8 ? 2 : TT_NBF2_MINW4) void k_nrb_bwd_fuse
             // (clamped to a byte: 0xff, the halo's key, is then below neither bound; an own pixel's row / column is below 255 anyway)
             const unsigned hl_ = (unsigned)(H - h0 + D), tl_ = (unsigned)(T - t0 + G::DP);
             const unsigned hlim = hl_ < 255u ? hl_ : 255u, tlim = tl_ < 255u ? tl_ : 255u;
-#pragma unroll
-            for (int s1 = 0; s1 < NS1; ++s1) {
-                const int c0 = wave * 64 + s1 * NT;
-                if (c0 >= NPX) break;
+            // One step = 64 consecutive pixels of the halo'd image for one wave.  SUMS = false: a step without a pixel of the tile proper (the
+            // halo rows above and below it) -- the chain and the dA1 store only; its mask would be 0 in every lane.
+            auto step1 = [&](const int s1, auto sums_c) {
+                constexpr bool SUMS = decltype(sums_c)::value;
+                const int c0 = wv * 64 + s1 * NT;
                 // the step's first pixel in a register the compiler cannot see through: what is derived from it is computed HERE, per step, and
                 // not once per kernel for all NS1 steps and kept (that is how the offsets came back as registers, and went to scratch)
                 unsigned step = s1 * NT;
                 asm volatile("" : "+v"(step));
-                const unsigned key = KEY_PER_STEP ? key_of((int)(q0 + step)) : (pkey2[s1 >> 1] >> (16 * (s1 & 1))) & 0xffffu, poff = poff_of(step);
-                const bool centre = (key & 0xffu) < hlim && (key >> 8) < tlim;
+                const unsigned poff = poff_of(step);
                 const vec_t hq = *reinterpret_cast<const vec_t*>(hs + poff);
                 const vec_t dq = *reinterpret_cast<const vec_t*>(gs + poff);
                 f32x4 z[NB], u[NB], gv[NB];
-                e16x4 gq4[NB];
+                unsigned gw[C / 2];                              // dA2 in 16 bits, two channels a word: the matrix operand AND the row for dW2
 #pragma unroll
                 for (int ob = 0; ob < NB; ++ob) {
                     z[ob] = f32x4{b2r[4 * ob], b2r[4 * ob + 1], b2r[4 * ob + 2], b2r[4 * ob + 3]};
@@ -1136,47 +1153,73 @@ __global__ __launch_bounds__(NT, C == 8 ? 2 : TT_NBF2_MINW4) void k_nrb_bwd_fuse
                 for (int ob = 0; ob < NB; ++ob) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) gv[ob][r] = (float)dq[4 * ob + r] * elu_dpre(z[ob][r]);
-                    gq4[ob] = __builtin_convertvector(gv[ob], e16x4);
+                    gw[2 * ob] = pack2_e16(gv[ob][0], gv[ob][1]);
+                    gw[2 * ob + 1] = pack2_e16(gv[ob][2], gv[ob][3]);
                 }
 #pragma unroll
                 for (int ob = 0; ob < NB; ++ob) {
                     u[ob] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int kb = 0; kb < NB; ++kb) u[ob] = mma4(A2T[ob][kb], __builtin_bit_cast(s16x4, gq4[kb]), u[ob]);
+                    for (int kb = 0; kb < NB; ++kb) u[ob] = mma4(A2T[ob][kb], __builtin_bit_cast(s16x4, (u32x2{gw[2 * kb], gw[2 * kb + 1]})), u[ob]);
                 }
-                const float m = centre ? 1.f : 0.f;              // sums only over this tile's own pixels
-                vec_t aq, gq;
+                float a1[C];
 #pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const float a1 = u[c >> 2][c & 3] * elu_dout((float)hq[c]);
-                    aq[c] = (e16)a1;
-                    gq[c] = gq4[c >> 2][c & 3];
-                    acc[c] = __builtin_fmaf(m, a1, acc[c]);
-                    acc[C + c] = __builtin_fmaf(m, gv[c >> 2][c & 3], acc[C + c]);
-                }
-                // dW2 += dA2 (x) h1 over the tile's own pixels as ONE matrix product per 64 pixels
-                *reinterpret_cast<vec_t*>(abuf + lane * G::PXB) = centre ? gq : zero_px;
-                __builtin_amdgcn_wave_barrier();
-                asm volatile("" ::: "memory");
-                const int so = 32 * (4 * g + trj) + 8 * trq;
-                const unsigned char* hb0 = hs + (wave * 64 + step) * G::PXB;         // the 64 pixels of this step, before dA1 replaces them
-                // transpose reads spelled out: in front of the builtin form the compiler places s_waitcnt vmcnt(0) (an LDS read it cannot
-                // prove disjoint from the x pieces still arriving by LDS-DMA), which is exactly the wait this kernel defers
-                const unsigned ga_ = lds_addr(abuf + so), ha_ = lds_addr(hb0 + so);
-                if constexpr (C == 8) {
-                    s16x4 glo, ghi, hlo, hhi;
-                    asm volatile("ds_read_b64_tr_b16 %0, %4\n\tds_read_b64_tr_b16 %1, %4 offset:512\n\tds_read_b64_tr_b16 %2, %5\n\t"
-                                 "ds_read_b64_tr_b16 %3, %5 offset:512\n\ts_waitcnt lgkmcnt(0)"
-                                 : "=&v"(glo), "=&v"(ghi), "=&v"(hlo), "=&v"(hhi) : "v"(ga_), "v"(ha_) : "memory");
-                    dw2m = mma32(__builtin_bit_cast(e16x8, __builtin_shufflevector(glo, ghi, 0, 1, 2, 3, 4, 5, 6, 7)),
-                                 __builtin_bit_cast(e16x8, __builtin_shufflevector(hlo, hhi, 0, 1, 2, 3, 4, 5, 6, 7)), dw2m);
+                for (int c = 0; c < C; ++c) a1[c] = u[c >> 2][c & 3] * elu_dout((float)hq[c]);
+                u32xh aq;
+#pragma unroll
+                for (int k = 0; k < C / 2; ++k) aq[k] = pack2_e16(a1[2 * k], a1[2 * k + 1]);
+                if constexpr (!SUMS) {
+                    // (only the image's last chunk is a partial one, and it is never a full step: KHI below)
+                    if (s1 * NT + 4 * 64 <= NPX || lane < NPX - c0) *reinterpret_cast<u32xh*>(hs + poff) = aq;
                 } else {
-                    s16x4 gt_, ht_;
-                    asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %3\n\ts_waitcnt lgkmcnt(0)"
-                                 : "=&v"(gt_), "=&v"(ht_) : "v"(ga_), "v"(ha_) : "memory");
-                    dw2m = mma16(gt_, ht_, dw2m);
+                    const unsigned key = KEY_PER_STEP ? key_of((int)(q0 + step)) : (pkey2[s1 >> 1] >> (16 * (s1 & 1))) & 0xffffu;
+                    const bool centre = (key & 0xffu) < hlim && (key >> 8) < tlim;
+                    const float m = centre ? 1.f : 0.f;              // sums only over this tile's own pixels
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        acc[c] = __builtin_fmaf(m, a1[c], acc[c]);
+                        acc[C + c] = __builtin_fmaf(m, gv[c >> 2][c & 3], acc[C + c]);
+                    }
+                    // dW2 += dA2 (x) h1 over the tile's own pixels as ONE matrix product per 64 pixels
+                    u32xh gm;
+#pragma unroll
+                    for (int k = 0; k < C / 2; ++k) gm[k] = centre ? gw[k] : 0u;
+                    *reinterpret_cast<u32xh*>(abuf + lane * G::PXB) = gm;
+                    __builtin_amdgcn_wave_barrier();
+                    asm volatile("" ::: "memory");
+                    const int so = 32 * (4 * g + trj) + 8 * trq;
+                    const unsigned char* hb0 = hs + (wv * 64 + step) * G::PXB;         // the 64 pixels of this step, before dA1 replaces them
+                    // transpose reads spelled out: in front of the builtin form the compiler places s_waitcnt vmcnt(0) (an LDS read it cannot
+                    // prove disjoint from the x pieces still arriving by LDS-DMA), which is exactly the wait this kernel defers
+                    const unsigned ga_ = lds_addr(abuf + so), ha_ = lds_addr(hb0 + so);
+                    if constexpr (C == 8) {
+                        s16x4 glo, ghi, hlo, hhi;
+                        asm volatile("ds_read_b64_tr_b16 %0, %4\n\tds_read_b64_tr_b16 %1, %4 offset:512\n\tds_read_b64_tr_b16 %2, %5\n\t"
+                                     "ds_read_b64_tr_b16 %3, %5 offset:512\n\ts_waitcnt lgkmcnt(0)"
+                                     : "=&v"(glo), "=&v"(ghi), "=&v"(hlo), "=&v"(hhi) : "v"(ga_), "v"(ha_) : "memory");
+                        dw2m = mma32(__builtin_bit_cast(e16x8, __builtin_shufflevector(glo, ghi, 0, 1, 2, 3, 4, 5, 6, 7)),
+                                     __builtin_bit_cast(e16x8, __builtin_shufflevector(hlo, hhi, 0, 1, 2, 3, 4, 5, 6, 7)), dw2m);
+                    } else {
+                        s16x4 gt_, ht_;
+                        asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %3\n\ts_waitcnt lgkmcnt(0)"
+                                     : "=&v"(gt_), "=&v"(ht_) : "v"(ga_), "v"(ha_) : "memory");
+                        dw2m = mma16(gt_, ht_, dw2m);
+                    }
+                    *reinterpret_cast<u32xh*>(hs + poff) = aq;
                 }
-                if (c0 + 64 <= NPX || lane < NPX - c0) *reinterpret_cast<vec_t*>(hs + poff) = aq;
+            };
+            // Which steps hold no pixel of the tile proper is fixed by (C, D): chunk k = 4 s1 + wave of 64 pixels lies wholly in front of the first own
+            // pixel for k < KLO and wholly behind the last one from KHI on.  The full chunks KLO .. KHI - 1 go round the four waves, so no wave runs more
+            // than one full step more than another, and the few-pixel tail chunk (behind at least D rows of halo) is never a full one.
+            constexpr int KLO = (D * G::RW + G::DP) / 64, KHI = ((D + G::TH - 1) * G::RW + G::DP + G::TW - 1) / 64 + 1;
+            static_assert((NPX - 1) / 64 >= KHI, "the tail chunk of phase 1 is a halo-only one");
+#pragma unroll
+            for (int s1 = 0; s1 < NS1; ++s1) {
+                if (wv * 64 + s1 * NT >= NPX) break;
+                if (4 * s1 + 3 < KLO || 4 * s1 >= KHI) step1(s1, std::false_type());
+                else if (4 * s1 >= KLO && 4 * s1 + 3 < KHI) step1(s1, std::true_type());
+                else if (wv >= KLO - 4 * s1 && wv < KHI - 4 * s1) step1(s1, std::true_type());
+                else step1(s1, std::false_type());
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // x has had all of phase 1 to arrive
