@@ -142,8 +142,31 @@ int tt_cqt_generic_forward(const tt_cqt_gplan* plan, const float* audio, float* 
 int tt_cqt_generic_inverse(const tt_cqt_gplan* plan, const float* coeffs, float* audio, void* scratch,
                            int B, int n_blocks, int in_complex, int normalize, void* stream);
 
+/* Adjoints of the transform (version 19): what autograd needs of CQT.encode / the raw synthesis, which the reference inherits as
+ * differentiable torch code from cqt_pytorch.  Both directions are real-linear and every window lies inside the open positive
+ * half-spectrum, so with a gradient w.r.t. complex values held as dL/dre + i dL/dim (torch's convention), N = block length and
+ * M = frames per block:
+ *   tt_cqt_forward_bwd   daudio  = (N / 2M) * synthesis of dcoeffs on the ANALYSIS windows (no inf-norm)
+ *   tt_cqt_inverse_bwd   dcoeffs = (2M / N) * analysis of daudio on the SYNTHESIS windows
+ * The same launches on the same bytes as the direction they run, the constant folded into a scaling that direction already does;
+ * layouts and the *_complex flags as in tt_cqt_forward / tt_cqt_inverse (dcoeffs takes the place of coeffs / out).  Fixed summation
+ * orders, no atomics: bit-identical from run to run.  Scratch: tt_cqt_scratch_bytes / tt_cqt_generic_scratch_bytes as above. */
+int tt_cqt_forward_bwd(const tt_cqt_plan* plan, const float* dcoeffs, float* daudio, void* scratch,
+                       int B, int n_blocks, int in_complex, void* stream);
+int tt_cqt_inverse_bwd(const tt_cqt_plan* plan, const float* daudio, float* dcoeffs, void* scratch,
+                       int B, int n_blocks, int out_complex, void* stream);
+/* Gradient of tt_cqt_forward_mag: audio (B, 1, n_blocks*66150) as given to the forward, dmag (B, 1, F, n_blocks*1024) -> daudio.  The
+ * band kernel recomputes c in registers, forms dc = dmag c / |c| (exactly 0 where |c| == 0, torch's norm backward) and transforms it
+ * in the same wave: neither the coefficients nor their gradient reach memory. */
+int tt_cqt_forward_mag_bwd(const tt_cqt_plan* plan, const float* audio, const float* dmag, float* daudio, void* scratch,
+                           int B, int n_blocks, void* stream);
+int tt_cqt_generic_forward_bwd(const tt_cqt_gplan* plan, const float* dcoeffs, float* daudio, void* scratch,
+                               int B, int n_blocks, int in_complex, void* stream);
+int tt_cqt_generic_inverse_bwd(const tt_cqt_gplan* plan, const float* daudio, float* dcoeffs, void* scratch,
+                               int B, int n_blocks, int out_complex, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
- * Convolution stack.  Replaces torch.nn.Conv2d / ConvTranspose2d / ELU as used by
+ * Convolution stack. Replaces torch.nn.Conv2d / ConvTranspose2d / ELU as used by
  * timbre_trap/framework/modules.py (ResidualConv2dBlock :721-777, EncoderBlock :597-655,
  * DecoderBlock :658-718, Encoder :396-483, Decoder :486-594) and their autograd backward.
  * ---------------------------------------------------------------------------------------------- */

@@ -16,6 +16,8 @@
 //                   4 bins per workgroup, no workgroup barrier.
 // The inverse runs the same machinery backwards (k_band_inv, k_spec_gather, the same two FFT
 // kernels through the conj trick, k_absmax / k_scale for the wrapper's inf-norm).
+// The adjoints (tt_cqt_forward_bwd, tt_cqt_inverse_bwd, tt_cqt_forward_mag_bwd, at the end of the file) are the same launches with
+// the two window tables exchanged; only k_band_mag_bwd, the magnitude gradient's band stage, is a kernel of its own.
 //
 // HBM traffic per block-clip (algorithmic): 264,600 B audio + 4,423,680 B coefficients.  The
 // spectra (2 x 264,600 B) stay in L2 / Infinity Cache between the three launches.
@@ -160,6 +162,8 @@ __global__ __launch_bounds__(FFT_ROWS_THREADS) void k_fft675_rows(const float2* 
 //   G[b][e] = W_49^(b e) * sum_a W_7^(a e) A[7a + b]          (thread = (column, b): 7 inputs -> 7 outputs)
 //   Z[e+7f] = sum_b W_7^(b f) G[b][e]                          (thread = (column, e): 7 inputs -> 7 outputs)
 // MODE 0: real-FFT split -> X[q][0..NC] (half spectrum of the 66150 real samples).
+// MODE 2: MODE 1 for the adjoint of the analysis (tt_cqt_forward_bwd, tt_cqt_forward_mag_bwd): its constant N / 2M = NC / M times the
+//         1 / NC of the tail is 1 / M, one multiplication as before, and there is no abs-max.
 // MODE 1: inverse tail  -> out[q][k] = conj(Z[k]) / NC  written as audio pairs; the workgroup's abs-max goes to *mx
 //         (CQT.decode's inf-norm, reference cqtwrapper.py:209-211) with one atomic per workgroup.  The maximum is taken on the bit
 //         patterns of |v|: non-negative floats order like their bits and a NaN (sign cleared) lies above +inf, so a NaN sample
@@ -235,8 +239,8 @@ __global__ __launch_bounds__(256) void k_fft49_cols(const float2* __restrict__ A
         for (int f = 0; f < 7; ++f) Zl[c1][e + 7 * f] = o[f];
     }
     __syncthreads();
-    if (MODE == 1) {
-        const float inv = 1.0f / (float)NC;
+    if (MODE >= 1) {
+        const float inv = (MODE == 2) ? 1.0f / (float)M : 1.0f / (float)NC;
         float2* o = out + q * NC;
         unsigned m = 0u;
         for (int i = tid; i < ncol * N2; i += 256) {
@@ -248,7 +252,7 @@ __global__ __launch_bounds__(256) void k_fft49_cols(const float2* __restrict__ A
             o[k1 + N1 * k2] = r;
             m = max(m, max(__float_as_uint(fabsf(r.x)), __float_as_uint(fabsf(r.y))));
         }
-        if (mx) {
+        if (MODE == 1 && mx) {
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
             if ((tid & 63) == 0) wmax[tid >> 6] = m;
@@ -406,7 +410,9 @@ __device__ __forceinline__ void fft1024_wave(float2 (&v)[16], float2* lds, const
 
 // forward band kernel: grid (ceil(F/4), Q); one wave per bin
 // MAG (tt_cqt_forward_mag): one (B,1,F,T) plane of |c| instead of the two planes -- the magnitude variants' encoder input
-template <bool COMPLEX_OUT, bool MAG = false>
+// ADJ (tt_cqt_inverse_bwd): the adjoint of the synthesis is this kernel on the dual windows (the caller passes them as `window`) with
+//     2 / N = 1 / NC in place of the 1 / M of the epilogue
+template <bool COMPLEX_OUT, bool MAG = false, bool ADJ = false>
 __global__ __launch_bounds__(256) void k_band_fwd(const float2* __restrict__ X, float* __restrict__ out,
                                                   const int4* __restrict__ bin_tab, const float* __restrict__ window,
                                                   const float2* __restrict__ tw1024, int F, int n_blocks) {
@@ -432,7 +438,7 @@ __global__ __launch_bounds__(256) void k_band_fwd(const float2* __restrict__ X, 
         v[a] = val;
     }
     fft1024_wave<true>(v, lds, tw1024, lane);
-    const float inv = 1.0f / (float)M;
+    const float inv = ADJ ? 1.0f / (float)NC : 1.0f / (float)M;
     const long b = q / n_blocks, blk = q - b * n_blocks;
     const long Tt = (long)n_blocks * M;
     // the transform leaves frame 64 r + lane in v[r]; one more wave-local LDS exchange gives every lane four CONSECUTIVE
@@ -474,6 +480,7 @@ __global__ __launch_bounds__(256) void k_band_fwd(const float2* __restrict__ X, 
 }
 
 // inverse band kernel: FFT of each bin's 1024 frames, times the dual window, to the ragged scratch S
+// (tt_cqt_forward_bwd: the same kernel with the analysis windows passed as `dual`)
 template <bool COMPLEX_IN>
 __global__ __launch_bounds__(256) void k_band_inv(const float* __restrict__ coeffs, float2* __restrict__ S,
                                                   const int4* __restrict__ bin_tab, const float* __restrict__ dual,
@@ -506,6 +513,60 @@ __global__ __launch_bounds__(256) void k_band_inv(const float* __restrict__ coef
         const int m = 64 * r + lane - bt.y;
         if (m >= 0 && m < bt.z) {
             const float g = dl[m];
+            s[m] = make_float2(v[r].x * g, v[r].y * g);
+        }
+    }
+}
+
+// Gradient of k_band_fwd<false, true> (tt_cqt_forward_mag_bwd), one wave per (bin, block-clip): the coefficients are recomputed in
+// registers exactly as the forward computes them, dc = dmag c / |c| (0 where |c| == 0, torch's norm backward) goes through the forward
+// 1024-point FFT in the same wave and LDS slice, and leaves as k_band_inv's output on the ANALYSIS windows: neither c nor dc reaches
+// memory.  The constant of the adjoint is in the tail (k_fft49_cols<2>).
+__global__ __launch_bounds__(256) void k_band_mag_bwd(const float2* __restrict__ X, const float* __restrict__ dmag, float2* __restrict__ S,
+                                                      const int4* __restrict__ bin_tab, const float* __restrict__ window,
+                                                      const float2* __restrict__ tw1024, int F, int n_blocks, int sum_len) {
+    __shared__ __attribute__((aligned(16))) float2 lds_all[4 * FFT_LDS_F2];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const long q = blockIdx.y;
+    const int bin = blockIdx.x * 4 + wave;
+    if (bin >= F) return;                            // wave-uniform; no workgroup barrier below
+    float2* lds = lds_all + wave * FFT_LDS_F2;
+    const int4 bt = bin_tab[bin];                    // {spec_start, pad, length, win_off}
+    const float2* x = X + q * XPAD + bt.x;
+    const float* w = window + bt.w;
+    const long b = q / n_blocks, blk = q - b * n_blocks;
+    const long Tt = (long)n_blocks * M;
+    const float* dm = dmag + (b * F + bin) * Tt + blk * M;
+    float2 v[16];
+    float gm[16];
+#pragma unroll
+    for (int a = 0; a < 16; ++a) {
+        const int m = 64 * a + lane - bt.y;          // index inside the window
+        float2 val = make_float2(0.f, 0.f);
+        if (m >= 0 && m < bt.z) {
+            const float2 xv = x[m];
+            const float g = w[m];
+            val = make_float2(xv.x * g, xv.y * g);
+        }
+        v[a] = val;
+        gm[a] = dm[64 * a + lane];                   // the upstream gradient of frame 64 a + lane, in flight under the transform
+    }
+    fft1024_wave<true>(v, lds, tw1024, lane);        // frame 64 r + lane in v[r]
+    const float inv = 1.0f / (float)M;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const float re = v[r].x * inv, im = v[r].y * inv;
+        const float n = sqrtf(re * re + im * im);    // |c| as the forward epilogue computes it
+        const float t = gm[r] / n;
+        v[r] = (n == 0.f) ? make_float2(0.f, 0.f) : make_float2(re * t, im * t);
+    }
+    fft1024_wave<false>(v, lds, tw1024, lane);       // window sample 64 r + lane in v[r]
+    float2* s = S + q * sum_len + bt.w;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int m = 64 * r + lane - bt.y;
+        if (m >= 0 && m < bt.z) {
+            const float g = w[m];
             s[m] = make_float2(v[r].x * g, v[r].y * g);
         }
     }
@@ -579,14 +640,8 @@ static int cqt_set_attrs() {
     return 0;
 }
 
-static int cqt_forward(const tt_cqt_plan* plan, const float* audio, float* out, void* scratch, int B, int n_blocks, int out_complex,
-                       bool mag, void* stream) {
-    if (!plan || !audio || !out || !scratch || B <= 0 || n_blocks <= 0) return TT_E_BADARG;
-    int rc = cqt_set_attrs();
-    if (rc) return rc;
-    hipStream_t st = tt_stream(stream);
-    const int Q = B * n_blocks, F = plan->n_bins;
-    Scratch s = carve(scratch, Q, plan->sum_len);
+// the analysis up to the half spectra X (both launches of the four-step transform)
+static int cqt_spectrum(const tt_cqt_plan* plan, const float* audio, const Scratch& s, int Q, hipStream_t st) {
     // audio (B,1,n_blocks*66150) is already [Q][66150] = [Q][NC] float2
     hipLaunchKernelGGL(k_fft675_rows, dim3(N2 / ROWS, Q), dim3(FFT_ROWS_THREADS), LDS_ROWS, st,
                        reinterpret_cast<const float2*>(audio), s.A,
@@ -596,21 +651,42 @@ static int cqt_forward(const tt_cqt_plan* plan, const float* audio, float* out, 
                        reinterpret_cast<const float2*>(plan->tw49), reinterpret_cast<const float2*>(plan->twN),
                        (unsigned*)nullptr);
     TT_LAUNCH_CHECK();
+    return 0;
+}
+
+// ADJ: the band stage of tt_cqt_inverse_bwd (the caller's `window` is the dual table)
+template <bool ADJ>
+static int cqt_bands_fwd(const tt_cqt_plan* plan, const float* window, const Scratch& s, float* out, int Q, int n_blocks, int out_complex,
+                         bool mag, hipStream_t st) {
+    const int F = plan->n_bins;
     dim3 grid((F + 3) / 4, Q);
-    if (mag)
-        hipLaunchKernelGGL((k_band_fwd<false, true>), grid, dim3(256), 0, st, s.X, out,
-                           reinterpret_cast<const int4*>(plan->bin_tab), plan->window,
+    if (mag && !ADJ)
+        hipLaunchKernelGGL((k_band_fwd<false, true, false>), grid, dim3(256), 0, st, s.X, out,
+                           reinterpret_cast<const int4*>(plan->bin_tab), window,
                            reinterpret_cast<const float2*>(plan->tw1024), F, n_blocks);
     else if (out_complex)
-        hipLaunchKernelGGL(k_band_fwd<true>, grid, dim3(256), 0, st, s.X, out,
-                           reinterpret_cast<const int4*>(plan->bin_tab), plan->window,
+        hipLaunchKernelGGL((k_band_fwd<true, false, ADJ>), grid, dim3(256), 0, st, s.X, out,
+                           reinterpret_cast<const int4*>(plan->bin_tab), window,
                            reinterpret_cast<const float2*>(plan->tw1024), F, n_blocks);
     else
-        hipLaunchKernelGGL(k_band_fwd<false>, grid, dim3(256), 0, st, s.X, out,
-                           reinterpret_cast<const int4*>(plan->bin_tab), plan->window,
+        hipLaunchKernelGGL((k_band_fwd<false, false, ADJ>), grid, dim3(256), 0, st, s.X, out,
+                           reinterpret_cast<const int4*>(plan->bin_tab), window,
                            reinterpret_cast<const float2*>(plan->tw1024), F, n_blocks);
     TT_LAUNCH_CHECK();
     return 0;
+}
+
+static int cqt_forward(const tt_cqt_plan* plan, const float* audio, float* out, void* scratch, int B, int n_blocks, int out_complex,
+                       bool mag, void* stream) {
+    if (!plan || !audio || !out || !scratch || B <= 0 || n_blocks <= 0) return TT_E_BADARG;
+    int rc = cqt_set_attrs();
+    if (rc) return rc;
+    hipStream_t st = tt_stream(stream);
+    const int Q = B * n_blocks;
+    Scratch s = carve(scratch, Q, plan->sum_len);
+    rc = cqt_spectrum(plan, audio, s, Q, st);
+    if (rc) return rc;
+    return cqt_bands_fwd<false>(plan, plan->window, s, out, Q, n_blocks, out_complex, mag, st);
 }
 
 extern "C" int tt_cqt_forward(const tt_cqt_plan* plan, const float* audio, float* out, void* scratch,
@@ -623,24 +699,10 @@ extern "C" int tt_cqt_forward_mag(const tt_cqt_plan* plan, const float* audio, f
     return cqt_forward(plan, audio, out, scratch, B, n_blocks, 0, true, stream);
 }
 
-extern "C" int tt_cqt_inverse(const tt_cqt_plan* plan, const float* coeffs, float* audio, void* scratch,
-                              int B, int n_blocks, int in_complex, int normalize, void* stream) {
-    if (!plan || !coeffs || !audio || !scratch || B <= 0 || n_blocks <= 0) return TT_E_BADARG;
-    int rc = cqt_set_attrs();
-    if (rc) return rc;
-    hipStream_t st = tt_stream(stream);
-    const int Q = B * n_blocks, F = plan->n_bins;
-    Scratch s = carve(scratch, Q, plan->sum_len);
-    dim3 grid((F + 3) / 4, Q);
-    if (in_complex)
-        hipLaunchKernelGGL(k_band_inv<true>, grid, dim3(256), 0, st, coeffs, s.S,
-                           reinterpret_cast<const int4*>(plan->bin_tab), plan->dual,
-                           reinterpret_cast<const float2*>(plan->tw1024), F, n_blocks, plan->sum_len);
-    else
-        hipLaunchKernelGGL(k_band_inv<false>, grid, dim3(256), 0, st, coeffs, s.S,
-                           reinterpret_cast<const int4*>(plan->bin_tab), plan->dual,
-                           reinterpret_cast<const float2*>(plan->tw1024), F, n_blocks, plan->sum_len);
-    TT_LAUNCH_CHECK();
+// the synthesis from the ragged scratch S on: overlap-add, the length-N real inverse, the inf-norm.  ADJ: the tail of the analysis
+// adjoints (constant 1 / M, no inf-norm)
+template <bool ADJ>
+static int cqt_synth_tail(const tt_cqt_plan* plan, const Scratch& s, float* audio, int Q, int normalize, hipStream_t st) {
     float2* Zc = s.X;   // reuse: [Q][NC]
     hipLaunchKernelGGL(k_spec_gather, dim3((NC + 255) / 256, Q), dim3(256), 0, st, s.S, Zc, plan->gat_off,
                        plan->gat_idx, reinterpret_cast<const float2*>(plan->twN), plan->sum_len);
@@ -648,6 +710,12 @@ extern "C" int tt_cqt_inverse(const tt_cqt_plan* plan, const float* coeffs, floa
     hipLaunchKernelGGL(k_fft675_rows, dim3(N2 / ROWS, Q), dim3(FFT_ROWS_THREADS), LDS_ROWS, st, Zc, s.A,
                        reinterpret_cast<const float2*>(plan->tw675), reinterpret_cast<const float2*>(plan->twNc));
     TT_LAUNCH_CHECK();
+    if (ADJ) {
+        hipLaunchKernelGGL(k_fft49_cols<2>, dim3(NTILES, Q), dim3(256), 0, st, s.A, reinterpret_cast<float2*>(audio),
+                           reinterpret_cast<const float2*>(plan->tw49), reinterpret_cast<const float2*>(plan->twN), (unsigned*)nullptr);
+        TT_LAUNCH_CHECK();
+        return 0;
+    }
     if (normalize) TT_HIP(hipMemsetAsync(s.mx, 0, 4, st));
     hipLaunchKernelGGL(k_fft49_cols<1>, dim3(NTILES, Q), dim3(256), 0, st, s.A, reinterpret_cast<float2*>(audio),
                        reinterpret_cast<const float2*>(plan->tw49), reinterpret_cast<const float2*>(plan->twN),
@@ -659,4 +727,76 @@ extern "C" int tt_cqt_inverse(const tt_cqt_plan* plan, const float* coeffs, floa
         TT_LAUNCH_CHECK();
     }
     return 0;
+}
+
+// `dual`: the synthesis windows, or (ADJ) the analysis windows
+template <bool ADJ>
+static int cqt_inverse(const tt_cqt_plan* plan, const float* dual, const float* coeffs, float* audio, void* scratch, int B, int n_blocks,
+                       int in_complex, int normalize, void* stream) {
+    if (!plan || !coeffs || !audio || !scratch || B <= 0 || n_blocks <= 0) return TT_E_BADARG;
+    int rc = cqt_set_attrs();
+    if (rc) return rc;
+    hipStream_t st = tt_stream(stream);
+    const int Q = B * n_blocks, F = plan->n_bins;
+    Scratch s = carve(scratch, Q, plan->sum_len);
+    dim3 grid((F + 3) / 4, Q);
+    if (in_complex)
+        hipLaunchKernelGGL(k_band_inv<true>, grid, dim3(256), 0, st, coeffs, s.S,
+                           reinterpret_cast<const int4*>(plan->bin_tab), dual,
+                           reinterpret_cast<const float2*>(plan->tw1024), F, n_blocks, plan->sum_len);
+    else
+        hipLaunchKernelGGL(k_band_inv<false>, grid, dim3(256), 0, st, coeffs, s.S,
+                           reinterpret_cast<const int4*>(plan->bin_tab), dual,
+                           reinterpret_cast<const float2*>(plan->tw1024), F, n_blocks, plan->sum_len);
+    TT_LAUNCH_CHECK();
+    return cqt_synth_tail<ADJ>(plan, s, audio, Q, normalize, st);
+}
+
+extern "C" int tt_cqt_inverse(const tt_cqt_plan* plan, const float* coeffs, float* audio, void* scratch,
+                              int B, int n_blocks, int in_complex, int normalize, void* stream) {
+    if (!plan) return TT_E_BADARG;
+    return cqt_inverse<false>(plan, plan->dual, coeffs, audio, scratch, B, n_blocks, in_complex, normalize, stream);
+}
+
+// ---- adjoints (version 19) -----------------------------------------------------------------------------------------------------------
+// Both directions are real-linear and every window lies inside the open positive half-spectrum, so with gradients w.r.t. complex
+// values held as dL/dre + i dL/dim the adjoint of each direction is the other direction on the other window table, times a constant:
+//   analysis^T  = (N / 2M) synthesis[window]      synthesis^T = (2M / N) analysis[dual]
+// The same launches on the same bytes as the direction they run; fixed summation orders, no atomics: bit-reproducible.
+
+extern "C" int tt_cqt_forward_bwd(const tt_cqt_plan* plan, const float* dcoeffs, float* daudio, void* scratch, int B, int n_blocks,
+                                  int in_complex, void* stream) {
+    if (!plan) return TT_E_BADARG;
+    return cqt_inverse<true>(plan, plan->window, dcoeffs, daudio, scratch, B, n_blocks, in_complex, 0, stream);
+}
+
+extern "C" int tt_cqt_inverse_bwd(const tt_cqt_plan* plan, const float* daudio, float* dcoeffs, void* scratch, int B, int n_blocks,
+                                  int out_complex, void* stream) {
+    if (!plan || !daudio || !dcoeffs || !scratch || B <= 0 || n_blocks <= 0) return TT_E_BADARG;
+    int rc = cqt_set_attrs();
+    if (rc) return rc;
+    hipStream_t st = tt_stream(stream);
+    const int Q = B * n_blocks;
+    Scratch s = carve(scratch, Q, plan->sum_len);
+    rc = cqt_spectrum(plan, daudio, s, Q, st);
+    if (rc) return rc;
+    return cqt_bands_fwd<true>(plan, plan->dual, s, dcoeffs, Q, n_blocks, out_complex, false, st);
+}
+
+extern "C" int tt_cqt_forward_mag_bwd(const tt_cqt_plan* plan, const float* audio, const float* dmag, float* daudio, void* scratch, int B,
+                                      int n_blocks, void* stream) {
+    if (!plan || !audio || !dmag || !daudio || !scratch || B <= 0 || n_blocks <= 0) return TT_E_BADARG;
+    int rc = cqt_set_attrs();
+    if (rc) return rc;
+    hipStream_t st = tt_stream(stream);
+    const int Q = B * n_blocks, F = plan->n_bins;
+    Scratch s = carve(scratch, Q, plan->sum_len);
+    rc = cqt_spectrum(plan, audio, s, Q, st);
+    if (rc) return rc;
+    // X is read here for the last time: the tail reuses its storage as Zc; S is the third region of the carve, free in any forward
+    hipLaunchKernelGGL(k_band_mag_bwd, dim3((F + 3) / 4, Q), dim3(256), 0, st, s.X, dmag, s.S,
+                       reinterpret_cast<const int4*>(plan->bin_tab), plan->window,
+                       reinterpret_cast<const float2*>(plan->tw1024), F, n_blocks, plan->sum_len);
+    TT_LAUNCH_CHECK();
+    return cqt_synth_tail<true>(plan, s, daudio, Q, 0, st);
 }

@@ -146,10 +146,10 @@ __global__ __launch_bounds__(GT) void k_g_band_gather(const float2* __restrict__
 }
 
 // out <- conj(W) / M in the wrapper's layout: planes (B, 2, F, n_blocks M) or interleaved complex (B, 1, F, n_blocks M)
-__global__ __launch_bounds__(GT) void k_g_band_out(const float2* __restrict__ w, float* __restrict__ out, int F, int n_blocks, int logM, int interleaved,
-                                                   long total) {
+// (k_g_band_out_adj, tt_cqt_generic_inverse_bwd: 2 / N in place of 1 / M, the constant of the synthesis' adjoint in the same multiplication)
+__device__ __forceinline__ void g_band_out(const float2* __restrict__ w, float* __restrict__ out, int F, int n_blocks, int logM, int interleaved,
+                                           long total, float inv) {
     const int M = 1 << logM;
-    const float inv = 1.f / (float)M;
     const long T = (long)n_blocks * M;
     for (long g = (long)blockIdx.x * GT + threadIdx.x; g < total; g += (long)gridDim.x * GT) {
         const int m = (int)(g & (M - 1));
@@ -168,6 +168,16 @@ __global__ __launch_bounds__(GT) void k_g_band_out(const float2* __restrict__ w,
             out[((b * 2 + 1) * F + f) * T + t] = im;
         }
     }
+}
+
+__global__ __launch_bounds__(GT) void k_g_band_out(const float2* __restrict__ w, float* __restrict__ out, int F, int n_blocks, int logM, int interleaved,
+                                                   long total) {
+    g_band_out(w, out, F, n_blocks, logM, interleaved, total, 1.f / (float)(1 << logM));
+}
+
+__global__ __launch_bounds__(GT) void k_g_band_out_adj(const float2* __restrict__ w, float* __restrict__ out, int F, int n_blocks, int logM, int interleaved,
+                                                       long total, int N) {
+    g_band_out(w, out, F, n_blocks, logM, interleaved, total, 2.f / (float)N);
 }
 
 // inverse: coefficients in the wrapper's layout -> v[q][f][m]
@@ -233,6 +243,18 @@ __global__ __launch_bounds__(GT) void k_g_audio(const float2* __restrict__ w, co
     if ((threadIdx.x & 63) == 0 && mx != 0u) atomicMax(peak, mx);
 }
 
+// the same samples for tt_cqt_generic_forward_bwd: the adjoint's N / 2M times the 2 / N above is 1 / M, and there is no abs-max
+__global__ __launch_bounds__(GT) void k_g_audio_adj(const float2* __restrict__ w, const float2* __restrict__ chirp, float* __restrict__ audio, int N, int logP,
+                                                    long total, int M) {                          // total = Q * N
+    const float sc = 1.f / (float)M;
+    for (long g = (long)blockIdx.x * GT + threadIdx.x; g < total; g += (long)gridDim.x * GT) {
+        const long q = g / N;
+        const int n = (int)(g - q * N);
+        const float2 c = chirp[n], z = w[(q << logP) + n];
+        audio[g] = (c.x * z.x + c.y * z.y) * sc;                       // Re(c conj(z))
+    }
+}
+
 __global__ __launch_bounds__(GT) void k_g_scale(float* __restrict__ audio, const unsigned* __restrict__ peak, long total) {
     const float p = __uint_as_float(peak[0]);
     if (p == 0.f) return;                                              // cqtwrapper.py:209: only when the maximum is non-zero (a NaN peak divides)
@@ -275,8 +297,10 @@ extern "C" int64_t tt_cqt_generic_scratch_bytes(const tt_cqt_gplan* plan, int n_
     return 256 + 2 * align256(work_elems(plan, n_clips) * 8) + align256((int64_t)n_clips * (plan->N / 2 + 1) * 8);
 }
 
-extern "C" int tt_cqt_generic_forward(const tt_cqt_gplan* plan, const float* audio, float* out, void* scratch, int B, int n_blocks,
-                                      int out_complex, void* stream) {
+// the analysis on the ragged table `window`; ADJ: the adjoint of the synthesis (`window` is the dual table, constant 2 / N)
+template <bool ADJ>
+static int g_forward(const tt_cqt_gplan* plan, const float* window, const float* audio, float* out, void* scratch, int B, int n_blocks,
+                     int out_complex, void* stream) {
     if (!plan_ok(plan) || !audio || !out || !scratch || B <= 0 || n_blocks <= 0) return TT_E_BADARG;
     hipStream_t st = tt_stream(stream);
     const long Q = (long)B * n_blocks;
@@ -298,18 +322,23 @@ extern "C" int tt_cqt_generic_forward(const tt_cqt_gplan* plan, const float* aud
     TT_LAUNCH_CHECK();
     cur = s.a; other = s.b;
     total = (Q * F) << logM;
-    hipLaunchKernelGGL(k_g_band_gather, dim3(blocks_for(total)), dim3(GT), 0, st, s.spec, reinterpret_cast<const int4*>(plan->bin_tab), plan->window, cur, F,
+    hipLaunchKernelGGL(k_g_band_gather, dim3(blocks_for(total)), dim3(GT), 0, st, s.spec, reinterpret_cast<const int4*>(plan->bin_tab), window, cur, F,
                        NH1, logM, total);
     TT_LAUNCH_CHECK();
     rc = run_fft(cur, other, reinterpret_cast<const float2*>(plan->twM), logM, Q * F, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_g_band_out, dim3(blocks_for(total)), dim3(GT), 0, st, cur, out, F, n_blocks, logM, out_complex, total);
+    if (ADJ)
+        hipLaunchKernelGGL(k_g_band_out_adj, dim3(blocks_for(total)), dim3(GT), 0, st, cur, out, F, n_blocks, logM, out_complex, total, N);
+    else
+        hipLaunchKernelGGL(k_g_band_out, dim3(blocks_for(total)), dim3(GT), 0, st, cur, out, F, n_blocks, logM, out_complex, total);
     TT_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int tt_cqt_generic_inverse(const tt_cqt_gplan* plan, const float* coeffs, float* audio, void* scratch, int B, int n_blocks,
-                                      int in_complex, int normalize, void* stream) {
+// the synthesis on the ragged table `dual`; ADJ: the adjoint of the analysis (`dual` is the window table, constant N / 2M, no abs-max)
+template <bool ADJ>
+static int g_inverse(const tt_cqt_gplan* plan, const float* dual, const float* coeffs, float* audio, void* scratch, int B, int n_blocks,
+                     int in_complex, int normalize, void* stream) {
     if (!plan_ok(plan) || !coeffs || !audio || !scratch || B <= 0 || n_blocks <= 0) return TT_E_BADARG;
     hipStream_t st = tt_stream(stream);
     const long Q = (long)B * n_blocks;
@@ -323,7 +352,7 @@ extern "C" int tt_cqt_generic_inverse(const tt_cqt_gplan* plan, const float* coe
     int rc = run_fft(cur, other, reinterpret_cast<const float2*>(plan->twM), logM, Q * F, st);
     if (rc) return rc;
     total = Q << logP;
-    hipLaunchKernelGGL(k_g_ola, dim3(blocks_for(total)), dim3(GT), 0, st, cur, reinterpret_cast<const int4*>(plan->bin_tab), plan->dual, plan->gat_off,
+    hipLaunchKernelGGL(k_g_ola, dim3(blocks_for(total)), dim3(GT), 0, st, cur, reinterpret_cast<const int4*>(plan->bin_tab), dual, plan->gat_off,
                        plan->gat_idx, plan->pos_bin, chirp, other, F, NH1, logM, logP, total);
     TT_LAUNCH_CHECK();
     { float2* t = cur; cur = other; other = t; }
@@ -333,13 +362,43 @@ extern "C" int tt_cqt_generic_inverse(const tt_cqt_gplan* plan, const float* coe
     TT_LAUNCH_CHECK();
     rc = run_fft(cur, other, reinterpret_cast<const float2*>(plan->twP), logP, Q, st);
     if (rc) return rc;
-    TT_HIP(hipMemsetAsync(s.peak, 0, 4, st));
+    if (!ADJ) TT_HIP(hipMemsetAsync(s.peak, 0, 4, st));
     total = Q * N;
-    hipLaunchKernelGGL(k_g_audio, dim3(blocks_for(total)), dim3(GT), 0, st, cur, chirp, audio, s.peak, N, logP, total);
+    if (ADJ)
+        hipLaunchKernelGGL(k_g_audio_adj, dim3(blocks_for(total)), dim3(GT), 0, st, cur, chirp, audio, N, logP, total, plan->M);
+    else
+        hipLaunchKernelGGL(k_g_audio, dim3(blocks_for(total)), dim3(GT), 0, st, cur, chirp, audio, s.peak, N, logP, total);
     TT_LAUNCH_CHECK();
-    if (normalize) {
+    if (!ADJ && normalize) {
         hipLaunchKernelGGL(k_g_scale, dim3(blocks_for(total)), dim3(GT), 0, st, audio, s.peak, total);
         TT_LAUNCH_CHECK();
     }
     return 0;
+}
+
+extern "C" int tt_cqt_generic_forward(const tt_cqt_gplan* plan, const float* audio, float* out, void* scratch, int B, int n_blocks,
+                                      int out_complex, void* stream) {
+    if (!plan) return TT_E_BADARG;
+    return g_forward<false>(plan, plan->window, audio, out, scratch, B, n_blocks, out_complex, stream);
+}
+
+extern "C" int tt_cqt_generic_inverse(const tt_cqt_gplan* plan, const float* coeffs, float* audio, void* scratch, int B, int n_blocks,
+                                      int in_complex, int normalize, void* stream) {
+    if (!plan) return TT_E_BADARG;
+    return g_inverse<false>(plan, plan->dual, coeffs, audio, scratch, B, n_blocks, in_complex, normalize, stream);
+}
+
+// adjoints (version 19; the derivation is in cqt.hip): each is the other direction on the other window table, the constant folded into
+// the scaling the pipeline ends with
+
+extern "C" int tt_cqt_generic_forward_bwd(const tt_cqt_gplan* plan, const float* dcoeffs, float* daudio, void* scratch, int B, int n_blocks,
+                                          int in_complex, void* stream) {
+    if (!plan) return TT_E_BADARG;
+    return g_inverse<true>(plan, plan->window, dcoeffs, daudio, scratch, B, n_blocks, in_complex, 0, stream);
+}
+
+extern "C" int tt_cqt_generic_inverse_bwd(const tt_cqt_gplan* plan, const float* daudio, float* dcoeffs, void* scratch, int B, int n_blocks,
+                                          int out_complex, void* stream) {
+    if (!plan) return TT_E_BADARG;
+    return g_forward<true>(plan, plan->dual, daudio, dcoeffs, scratch, B, n_blocks, out_complex, stream);
 }

@@ -4,6 +4,11 @@ attributes (``sample_rate, hop_length, n_bins, midi_freqs, block_length, max_win
 methods, with the transform itself (``cqt_pytorch.CQT.encode/decode`` in the reference) computed by
 the gfx950 kernels of csrc/cqt.hip through the C ABI ``tt_cqt_forward`` / ``tt_cqt_inverse``.
 
+``encode``, ``analyze``, ``synthesize`` and ``magnitude`` take part in autograd, as the torch code the reference inherits from
+``cqt_pytorch`` does: their backward is the other direction of the transform on the other window table (``tt_cqt_forward_bwd`` /
+``tt_cqt_inverse_bwd`` / ``tt_cqt_forward_mag_bwd``; derivation in DESIGN.md 6j).  ``forward`` and ``decode`` stay detached: the
+reference wraps exactly those two in ``torch.no_grad()`` (cqtwrapper.py:65, :199).
+
 The frame/time helpers (reference :215-308) stay pure Python/NumPy: the datasets call them from
 DataLoader worker processes, so they must not touch the HIP runtime, and the object stays
 fork- and pickle-safe (no library handle is stored on it).
@@ -15,6 +20,7 @@ import math
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from .. import _hip
 from . import nsgt_plan, ops
@@ -24,6 +30,90 @@ _GENERIC_TABLES = ('chirp', 'bfilt', 'twP', 'twM', 'bin_tab', 'window', 'dual', 
 # True: also the reference configuration (3 s @ 22.05 kHz) runs on the any-block-length kernels (csrc/cqt_generic.hip) -- for tests
 # that hold the two paths against each other; read when a CQT is constructed
 FORCE_GENERIC = False
+
+
+def _wants_grad(t):
+    return torch.is_grad_enabled() and t.requires_grad
+
+
+# ---- autograd (kept here, not in ops: they bracket no bench event and take an unscaled gradient) --------------------------------------------
+# fp32 inside autocast regions; the gradient is made contiguous fp32 / complex64 before the call (it commonly arrives through
+# to_real's transposed view); no double backward.
+
+class _AnalysisFn(torch.autograd.Function):
+    """audio -> coefficients (CQT._transform); backward: tt_cqt_forward_bwd, the synthesis on the analysis windows times N / 2M."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
+    def forward(ctx, audio, cq, complex_out):
+        ctx.cq, ctx.complex_out, ctx.shape, ctx.dtype = cq, complex_out, audio.shape, audio.dtype
+        return cq._transform(audio, complex_out)
+
+    @staticmethod
+    @once_differentiable
+    @torch.amp.custom_bwd(device_type='cuda')
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        cq = ctx.cq
+        if ctx.complex_out:
+            g = g.resolve_conj().to(torch.complex64).reshape(-1, 1, cq.n_bins, g.size(-1))
+        else:
+            g = g.to(torch.float32).reshape(-1, 2, cq.n_bins, g.size(-1))
+        da = cq._synthesis(g, False, adjoint=True)
+        return da.reshape(ctx.shape).to(ctx.dtype), None, None
+
+
+class _SynthesisFn(torch.autograd.Function):
+    """coefficients -> audio without the inf-norm (CQT._decode_raw); backward: tt_cqt_inverse_bwd, the analysis on the dual windows
+    times 2M / N, in the layout the coefficients came in."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
+    def forward(ctx, coefficients, cq):
+        ctx.cq, ctx.is_complex, ctx.shape, ctx.dtype = cq, coefficients.is_complex(), coefficients.shape, coefficients.dtype
+        return cq._synthesis(coefficients, False)
+
+    @staticmethod
+    @once_differentiable
+    @torch.amp.custom_bwd(device_type='cuda')
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        dc = ctx.cq._analysis(g.to(torch.float32).reshape(ctx.shape[0], -1), ctx.is_complex, adjoint=True)
+        return dc.reshape(ctx.shape).to(ctx.dtype), None
+
+
+class _MagnitudeFn(torch.autograd.Function):
+    """audio -> |c| (tt_cqt_forward_mag); backward: tt_cqt_forward_mag_bwd on the saved audio -- the coefficients are recomputed in
+    registers, neither they nor their gradient reach memory."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
+    def forward(ctx, audio, cq):
+        ctx.cq, ctx.shape, ctx.dtype = cq, audio.shape, audio.dtype
+        ctx.save_for_backward(audio)
+        return cq._magnitude(audio)
+
+    @staticmethod
+    @once_differentiable
+    @torch.amp.custom_bwd(device_type='cuda')
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        cq = ctx.cq
+        audio, = ctx.saved_tensors
+        a, _ = cq._prepare_audio(audio)
+        B, n_blocks = a.size(0), a.size(1) // cq.block_length
+        g = g.to(torch.float32).reshape(B, cq.n_bins, n_blocks * cq.max_window_length).contiguous()
+        lib = _hip.lib()
+        ps = cq._plan_struct(a.device)
+        scratch = cq._scratch(lib, ps, B * n_blocks, a.device)
+        da = torch.empty_like(a)
+        with _hip.timed('cqt_forward_mag_bwd'):
+            _hip.check(lib.tt_cqt_forward_mag_bwd(ctypes.byref(ps), _hip.ptr(a), _hip.ptr(g), _hip.ptr(da), _hip.ptr(scratch), B, n_blocks,
+                                                  _hip.stream_ptr()), 'tt_cqt_forward_mag_bwd')
+        return da.reshape(ctx.shape).to(ctx.dtype), None
 
 
 class CQT(nn.Module):
@@ -105,32 +195,59 @@ class CQT(nn.Module):
         a = audio.reshape(-1, audio.size(-1)).to(torch.float32).contiguous()
         return a, lead
 
-    def _transform(self, audio, complex_out):
-        a, lead = self._prepare_audio(audio)
+    def _analysis(self, a, complex_out, adjoint=False):
+        """a (B, n_blocks N) contiguous fp32 -> (B, 2, F, T) planes or complex (B, 1, F, T).  ``adjoint``: the gradient of the synthesis
+        w.r.t. its coefficients instead (tt_cqt_inverse_bwd: the same pipeline on the dual windows, times 2M / N)."""
+        a = a.contiguous()
         B, n_blocks = a.size(0), a.size(1) // self.block_length
         T = n_blocks * self.max_window_length
         lib = _hip.lib()
         ps = self._plan_struct(a.device)
         scratch = self._scratch(lib, ps, B * n_blocks, a.device)
-        forward = lib.tt_cqt_forward if self._fast else lib.tt_cqt_generic_forward
+        if adjoint:
+            entry, name = (lib.tt_cqt_inverse_bwd if self._fast else lib.tt_cqt_generic_inverse_bwd), 'cqt_inverse_bwd'
+        else:
+            entry, name = (lib.tt_cqt_forward if self._fast else lib.tt_cqt_generic_forward), 'cqt_forward'
         if complex_out:
             out = torch.empty((B, 1, self.n_bins, T, 2), dtype=torch.float32, device=a.device)
         else:
             out = torch.empty((B, 2, self.n_bins, T), dtype=torch.float32, device=a.device)
-        with _hip.timed('cqt_forward'):
-            _hip.check(forward(ctypes.byref(ps), _hip.ptr(a), _hip.ptr(out), _hip.ptr(scratch),
-                               B, n_blocks, int(complex_out), _hip.stream_ptr()), 'tt_cqt_forward')
-        if complex_out:
-            out = torch.view_as_complex(out)
+        with _hip.timed(name):
+            _hip.check(entry(ctypes.byref(ps), _hip.ptr(a), _hip.ptr(out), _hip.ptr(scratch),
+                             B, n_blocks, int(complex_out), _hip.stream_ptr()), 'tt_' + name)
+        return torch.view_as_complex(out) if complex_out else out
+
+    def _transform(self, audio, complex_out):
+        a, lead = self._prepare_audio(audio)
+        out = self._analysis(a, complex_out)
         # (B,1,N) input -> lead == (B,1): the channel dim of the reference output replaces it
         if len(lead) != 2:
             out = out.reshape(*lead, *out.shape[1:])
         return out
 
     def encode(self, audio):
-        """audio (B x 1 x N) -> complex coefficients (B x 1 x F x T)   (cqtwrapper.py:67, sonify.py:94)."""
+        """audio (B x 1 x N) -> complex coefficients (B x 1 x F x T)   (cqtwrapper.py:67, sonify.py:94).  Differentiable w.r.t. the
+        audio, as ``cqt_pytorch.CQT.encode`` is."""
+        if _wants_grad(audio):
+            return _AnalysisFn.apply(audio, self, True)
         with torch.no_grad():
             return self._transform(audio, True)
+
+    def analyze(self, audio):
+        """The values and layout of ``forward`` (B x 2 x F x T real/imaginary planes, contiguous), taking part in autograd: what
+        ``to_real(encode(audio))`` is in the reference, without the transposed view."""
+        if _wants_grad(audio):
+            return _AnalysisFn.apply(audio, self, False)
+        with torch.no_grad():
+            return self._transform(audio, False)
+
+    def synthesize(self, coefficients):
+        """The raw synthesis ``cqt_pytorch.CQT.decode`` is (``super().decode`` at reference cqtwrapper.py:207): real (B x 2 x F x T) or
+        complex (B x 1 x F x T) coefficients -> audio (B x 1 x T), no division by the infinity norm; differentiable w.r.t. the
+        coefficients."""
+        if _wants_grad(coefficients):
+            return _SynthesisFn.apply(coefficients, self)
+        return self._decode(coefficients, False)
 
     def forward(self, audio):
         """
@@ -146,10 +263,18 @@ class CQT(nn.Module):
         ``to_magnitude(forward(audio))`` in one pass: audio (B x 1 x N) -> magnitudes (B x F x T), the input of the magnitude variants
         (reference modules.py:948, :1019).  The reference configuration writes |c| from the transform's own epilogue
         (tt_cqt_forward_mag: the two coefficient planes never reach memory); other block lengths compose the any-length transform with
-        tt_magnitude.
+        tt_magnitude.  Differentiable w.r.t. the audio: tt_cqt_forward_mag_bwd on the saved audio, or (other block lengths) ``encode``
+        composed with torch's norm.
         """
         if not self._fast:
+            if _wants_grad(audio):
+                return self.to_real(self.encode(audio)).norm(p=2, dim=-3)
             return self.to_magnitude(self.forward(audio))
+        if _wants_grad(audio):
+            return _MagnitudeFn.apply(audio, self)
+        return self._magnitude(audio)
+
+    def _magnitude(self, audio):
         with torch.no_grad():
             a, lead = self._prepare_audio(audio)
             B, n_blocks = a.size(0), a.size(1) // self.block_length
@@ -181,27 +306,38 @@ class CQT(nn.Module):
 
     def _decode(self, coefficients, normalize):
         with torch.no_grad():
-            _hip.require_cuda(coefficients)
-            is_complex = coefficients.is_complex()
-            if is_complex:
-                c = torch.view_as_real(coefficients.to(torch.complex64).contiguous())
-                B = c.size(0)
-                T = c.size(-2)
-            else:
-                c = coefficients.to(torch.float32).contiguous()
-                B = c.size(0)
-                T = c.size(-1)
-            if T % self.max_window_length:
-                raise ValueError('frame count %d is not a multiple of %d' % (T, self.max_window_length))
-            n_blocks = T // self.max_window_length
-            lib = _hip.lib()
-            ps = self._plan_struct(c.device)
-            scratch = self._scratch(lib, ps, B * n_blocks, c.device)
-            inverse = lib.tt_cqt_inverse if self._fast else lib.tt_cqt_generic_inverse
-            audio = torch.empty((B, 1, n_blocks * self.block_length), dtype=torch.float32, device=c.device)
-            with _hip.timed('cqt_inverse'):
-                _hip.check(inverse(ctypes.byref(ps), _hip.ptr(c), _hip.ptr(audio), _hip.ptr(scratch),
-                                   B, n_blocks, int(is_complex), int(bool(normalize)), _hip.stream_ptr()), 'tt_cqt_inverse')
+            return self._synthesis(coefficients, normalize)
+
+    def _synthesis(self, coefficients, normalize, adjoint=False):
+        """Coefficients (B, 2, F, T) or complex (B, 1, F, T) -> audio (B, 1, n_blocks N).  ``adjoint``: the gradient of the analysis
+        w.r.t. its audio instead (tt_cqt_forward_bwd: the same pipeline on the analysis windows, times N / 2M, no inf-norm)."""
+        _hip.require_cuda(coefficients)
+        is_complex = coefficients.is_complex()
+        if is_complex:
+            c = torch.view_as_real(coefficients.to(torch.complex64).contiguous())
+            B = c.size(0)
+            T = c.size(-2)
+        else:
+            c = coefficients.to(torch.float32).contiguous()
+            B = c.size(0)
+            T = c.size(-1)
+        if T % self.max_window_length:
+            raise ValueError('frame count %d is not a multiple of %d' % (T, self.max_window_length))
+        n_blocks = T // self.max_window_length
+        lib = _hip.lib()
+        ps = self._plan_struct(c.device)
+        scratch = self._scratch(lib, ps, B * n_blocks, c.device)
+        audio = torch.empty((B, 1, n_blocks * self.block_length), dtype=torch.float32, device=c.device)
+        if adjoint:
+            entry = lib.tt_cqt_forward_bwd if self._fast else lib.tt_cqt_generic_forward_bwd
+            with _hip.timed('cqt_forward_bwd'):
+                _hip.check(entry(ctypes.byref(ps), _hip.ptr(c), _hip.ptr(audio), _hip.ptr(scratch),
+                                 B, n_blocks, int(is_complex), _hip.stream_ptr()), 'tt_cqt_forward_bwd')
+            return audio
+        inverse = lib.tt_cqt_inverse if self._fast else lib.tt_cqt_generic_inverse
+        with _hip.timed('cqt_inverse'):
+            _hip.check(inverse(ctypes.byref(ps), _hip.ptr(c), _hip.ptr(audio), _hip.ptr(scratch),
+                               B, n_blocks, int(is_complex), int(bool(normalize)), _hip.stream_ptr()), 'tt_cqt_inverse')
         return audio
 
     # ---- layout helpers (reference cqtwrapper.py:74-182), stock tensor views ----------------------
