@@ -240,7 +240,30 @@ int tt_resblock_bwd(const float* x, const float* h1, const float* dy, const floa
  *   tt_wide_rb_fwd  y = ELU(W2 . ELU(W1 (*)_dil x + b1) + b2) + x ; h1 (may be NULL) = ELU(W1 (*) x + b1) saved for backward
  *   tt_wide_rb_bwd  from x, h1, dy: dx (written), dw1 / db1 / dw2 / db2 (fp32, accumulated +=); ws = tt_wide_scratch_bytes
  *                   bytes of scratch (C = 32: dL/d(conv1 pre-activation) in bf16, then per-workgroup partial gradients; C = 4, 8, 16
- *                   keep that tensor in LDS and need the partial gradients only -- C = 16: tt_wide_onepass_scratch_bytes). */
+ *                   keep that tensor in LDS and need the partial gradients only -- C = 16: tt_wide_onepass_scratch_bytes).
+ * Alignment and smallest planes of the cl16 entry points, as far as tests/test_gpu_cl16_parity.py holds them (element-wise float64
+ * parity through this ABI in both element types, guard bands of NaN and of a large finite value around every operand, planes down
+ * to one pixel).  A cl16 pointer that misses its requirement is refused with TT_E_BADARG before anything is launched:
+ *   tt_wide_pack / tt_wide_unpack   the cl16 side (out / in) 16-byte aligned; the fp32 planar side 4 bytes.  Any H, T > 0 (T even at C = 4).
+ *   tt_gate16, tt_skip_join16_*, tt_scaled_add16, tt_dot16   every 16-bit pointer 16-byte aligned; s, ds, out (fp32) 4 bytes.
+ *   tt_convin16[_1]_*, tt_convout16[_1]_*   cl16 tensors 8-byte aligned (one pixel of 4 channels; a batch half of an odd plane is no
+ *                   more than that); every fp32 operand and ws 4 bytes -- the 16-byte staging of a planar operand is chosen per call
+ *                   where T % 4 == 0 AND that operand (x; dy and the saved y of tt_convout16[_1]_bwd) is 16-byte aligned, any other
+ *                   call stages by 4-byte loads with the same results within rounding.  Any H, T > 0.
+ *   tt_latent16_*   every cl16 pointer (in, gy, g, out) and ws 16-byte aligned (LDS-DMA on g and on the operands prepared in ws);
+ *                   z, w, bias, out (fp32), dw, db 4 bytes.  T % 16 == 0, E >= 1, B >= 1, D >= 1.
+ *   tt_sconv16_*, tt_tconv16_*   every cl16 pointer (x, y, dy / g, dx) 16-byte aligned (LDS-DMA on the un-gated operand of the weight
+ *                   gradient, both operands in the pregated forms; 16-byte pieces elsewhere); w, b, dw, db and ws (fp32 partials)
+ *                   4 bytes.  tt_sconv16_*: H >= 4 (TT_E_BADARG below), any T > 0 (even at C = 4); tt_tconv16_*: any H, T > 0.
+ *   tt_wide_rb_fwd[_join], tt_wide_rb_bwd, _bwd_onepass, _bwd_fused, tt_wide_level_bwd[_gated[_join]]   every cl16 pointer (x, y, h1,
+ *                   skip, dy, dx, tmp0, tmp1, skip_g, each x[i] / h1[i] of a level) and ws 16-byte aligned (LDS-DMA on x, h1, dy and
+ *                   on the dA1 region of ws; 16-byte pieces elsewhere); the level call tests all of them before its first launch.
+ *                   w1, b1, w2, b2, skip weights and the fp32 gradients 4 bytes.  Any H, T > 0 (T even at C = 4): planes smaller than
+ *                   the halo are valid, taps outside the image contribute nothing -- read from the index arithmetic of every kernel
+ *                   behind these entry points (the test file's docstring, per kernel) and run down to (1, 2) (block) and (3, 6)
+ *                   (level).  ws at C = 4, 8, 16 holds fp32 partials only; the 16 bytes are asked at every width all the same.
+ * The level calls are held there as the claims below state them: tt_wide_level_bwd bit-identical to block-by-block calls, the gated
+ * forms against the plain call. */
 int64_t tt_wide_scratch_bytes(int B, int C, int H, int T);
 int tt_wide_pack(const float* x, void* out, int B, int C, int H, int T, void* stream);
 int tt_wide_unpack(const void* in, float* y, int B, int C, int H, int T, void* stream);
@@ -292,7 +315,7 @@ int tt_wide_level_bwd_gated_join(int nblocks, const void* const* x, const void* 
                                  float* const* db1, float* const* dw2, float* const* db2, void* ws, int B, int C, int H, int T,
                                  const int* dilations, const void* skip_g, int skip_reps, const float* skip_weights, int skip_idx,
                                  float* skip_dw, void* stream);
-/* g *= ELU'(y) in place on n 16-bit elements (n % 8 == 0): the same factor for a gradient that reaches such a layer by another way
+/* g *= ELU'(y) in place on n 16-bit elements (n % 8 == 0, both pointers 16-byte aligned; else TT_E_BADARG): the same factor for a gradient that reaches such a layer by another way
  * (a skip connection, a caller's own use of an encoder embedding; ops.GateTapFn). */
 int tt_gate16(void* g, const void* y, int64_t n, void* stream);
 /* The whole backward of one block in ONE pass from x and dy only (csrc/conv_level_bf16.hip; C = 16, 32, else
@@ -372,7 +395,8 @@ int tt_latent16_expand(const float* z, int Dz, float fill, const float* w, const
  *   tt_latent16_contract_pregated, tt_latent16_wgrad_pregated   backward of Decoder.convin from g = dy * ELU'(y), as
  *                                 tt_tconv16_bwd_pregated(gate_dx = 1) leaves it; y is not read.  The bias gradient rides as the weight
  *                                 gradient's row of a constant-1 input row: needs D < 48 (CT = 32) / D < 144 (CT = 64), else
- *                                 TT_E_UNSUPPORTED. */
+ *                                 TT_E_UNSUPPORTED -- from BOTH entry points (the pair is one backward; the contraction used to run
+ *                                 there), with nothing written. */
 /* 1 where the two pregated entry points below take a head of CT channels and D input channels (they need a free input row of the weight
  * gradient's tile for the bias gradient), else 0 -- what a caller asks before it promises the gate (ops.LatDec16Fn). */
 int tt_latent16_pregated_ok(int CT, int D);

@@ -149,6 +149,10 @@ constexpr int REL = 16, RSL = 64;
 // 42 / 164 blocks on the chip at C = 4 / 8 (REL x RSL would leave 11 / 41)
 constexpr int NREL = 4, NRSL = 256;
 
+// true where every pointer is a multiple of `bytes` (a power of two); NULL counts as aligned.  The alignment contract of the cl16 entry
+// points (include/ttrap.h) is tested with this on the host, before anything is launched.
+template <class... P> inline bool ptrs_aligned(uintptr_t bytes, P... p) { return (((uintptr_t)p | ... | (uintptr_t)0) & (bytes - 1)) == 0; }
+
 inline int grid_for(int ntiles, int lds_bytes, int max_per_cu) {
     int per = lds_bytes > 0 ? (160 * 1024) / lds_bytes : max_per_cu;
     if (per > max_per_cu) per = max_per_cu;

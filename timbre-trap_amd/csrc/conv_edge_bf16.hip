@@ -680,6 +680,11 @@ constexpr int EDGE_MAX_WG = 1024;
 
 inline bool edge_ok(int B, int H, int T) { return B > 0 && H > 0 && T > 0 && (long)H * T * 4 < (1l << 31); }
 inline void edge_tiles(int B, int H, int T, int& th, int& tt, int& n) { th = (H + ETH - 1) / ETH; tt = (T + ETW - 1) / ETW; n = B * th * tt; }
+// cl16 tensors are read and written one pixel (4 channels = 8 bytes) at a time
+template <class... P> inline bool edge_cl_ok(P... p) { return ptrs_aligned(8, p...); }
+// the float4 staging of a planar fp32 operand (StagePlanar<.., VEC = true>) needs whole 16-byte groups: T % 4 == 0 AND the operand (with the
+// saved output the gate reads at the same place) on a 16-byte boundary -- caller data, e.g. a slice of a CQT output; otherwise 4-byte loads
+template <class... P> inline bool edge_vec(int T, P... p) { return T % 4 == 0 && ptrs_aligned(16, p...); }
 inline int edge_grid(int ntiles) { const int cap = 4 * tt_cus(); const int g = ntiles < cap ? ntiles : cap; return g < EDGE_MAX_WG ? g : EDGE_MAX_WG; }
 
 }  // namespace
@@ -689,9 +694,9 @@ extern "C" {
 int64_t tt_edge16_scratch_bytes(void) { return (int64_t)EDGE_MAX_WG * NPARTW * 4; }
 
 int tt_convin16_fwd(const float* x, const float* w, const float* b, void* y, int B, int H, int T, void* stream) {
-    if (!x || !w || !b || !y || !edge_ok(B, H, T)) return TT_E_BADARG;
+    if (!x || !w || !b || !y || !edge_ok(B, H, T) || !edge_cl_ok(y)) return TT_E_BADARG;
     int th, tt, n; edge_tiles(B, H, T, th, tt, n);
-    if (T % 4 == 0) hipLaunchKernelGGL(k_cin_fwd<true>, dim3(edge_grid(n)), dim3(NT), 0, tt_stream(stream), x, w, b, (e16*)y, H, T, th, tt, n);
+    if (edge_vec(T, x)) hipLaunchKernelGGL(k_cin_fwd<true>, dim3(edge_grid(n)), dim3(NT), 0, tt_stream(stream), x, w, b, (e16*)y, H, T, th, tt, n);
     else hipLaunchKernelGGL(k_cin_fwd<false>, dim3(edge_grid(n)), dim3(NT), 0, tt_stream(stream), x, w, b, (e16*)y, H, T, th, tt, n);
     TT_LAUNCH_CHECK();
     return 0;
@@ -699,11 +704,11 @@ int tt_convin16_fwd(const float* x, const float* w, const float* b, void* y, int
 
 int tt_convin16_bwd(const float* x, const void* y, const void* dy, const float* w, float* dx, float* dw, float* db, void* ws, int B,
                     int H, int T, void* stream) {
-    if (!x || !dy || !w || !dw || !db || !ws || !edge_ok(B, H, T)) return TT_E_BADARG;       // y == NULL: dy is already gated
+    if (!x || !dy || !w || !dw || !db || !ws || !edge_ok(B, H, T) || !edge_cl_ok(y, dy)) return TT_E_BADARG;       // y == NULL: dy is already gated
     int th, tt, n; edge_tiles(B, H, T, th, tt, n);
     const int grid = edge_grid(n);
     hipStream_t st = tt_stream(stream);
-    const bool vec = T % 4 == 0;
+    const bool vec = edge_vec(T, x);
 #define CIN_BWD(DX_, V_, P_) hipLaunchKernelGGL((k_cin_bwd<DX_, V_, P_>), dim3(grid), dim3(NT), 0, st, x, (const e16*)y, (const e16*)dy, w, dx, (float*)ws, H, T, th, tt, n, tt_loss_unscale())
     if (y) {
         if (dx) { if (vec) CIN_BWD(true, true, false); else CIN_BWD(true, false, false); }
@@ -720,7 +725,7 @@ int tt_convin16_bwd(const float* x, const void* y, const void* dy, const float* 
 }
 
 int tt_convout16_fwd(const void* x, const float* w, const float* b, float* y, int B, int H, int T, void* stream) {
-    if (!x || !w || !b || !y || !edge_ok(B, H, T)) return TT_E_BADARG;
+    if (!x || !w || !b || !y || !edge_ok(B, H, T) || !edge_cl_ok(x)) return TT_E_BADARG;
     int th, tt, n; edge_tiles(B, H, T, th, tt, n);
     hipLaunchKernelGGL(k_cout_fwd, dim3(edge_grid(n)), dim3(NT), 0, tt_stream(stream), (const e16*)x, w, b, y, H, T, th, tt, n);
     TT_LAUNCH_CHECK();
@@ -729,11 +734,11 @@ int tt_convout16_fwd(const void* x, const float* w, const float* b, float* y, in
 
 int tt_convout16_bwd(const void* x, const float* dy, const float* w, void* dx, float* dw, float* db, void* ws, int B, int H, int T,
                      void* stream) {
-    if (!x || !dy || !w || !dx || !dw || !db || !ws || !edge_ok(B, H, T)) return TT_E_BADARG;
+    if (!x || !dy || !w || !dx || !dw || !db || !ws || !edge_ok(B, H, T) || !edge_cl_ok(x, dx)) return TT_E_BADARG;
     int th, tt, n; edge_tiles(B, H, T, th, tt, n);
     const int grid = edge_grid(n);
     hipStream_t st = tt_stream(stream);
-    if (T % 4 == 0) hipLaunchKernelGGL(k_cout_bwd<true>, dim3(grid), dim3(NT), 0, st, (const e16*)x, dy, w, (e16*)dx, (float*)ws, H, T, th, tt, n, tt_loss_scale());
+    if (edge_vec(T, dy)) hipLaunchKernelGGL(k_cout_bwd<true>, dim3(grid), dim3(NT), 0, st, (const e16*)x, dy, w, (e16*)dx, (float*)ws, H, T, th, tt, n, tt_loss_scale());
     else hipLaunchKernelGGL(k_cout_bwd<false>, dim3(grid), dim3(NT), 0, st, (const e16*)x, dy, w, (e16*)dx, (float*)ws, H, T, th, tt, n, tt_loss_scale());
     TT_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_edge_reduce, dim3(2), dim3(1024), 0, st, (const float*)ws, grid, dw, db, 2, 1.f);   // dW, db from the fp32 dy itself
@@ -743,9 +748,9 @@ int tt_convout16_bwd(const void* x, const float* dy, const float* w, void* dx, f
 
 // ---- the one-channel edges of the magnitude variants (version 8) ----------------------------------------------------------------
 int tt_convin16_1_fwd(const float* x, const float* w, const float* b, void* y, int B, int H, int T, void* stream) {
-    if (!x || !w || !b || !y || !edge_ok(B, H, T)) return TT_E_BADARG;
+    if (!x || !w || !b || !y || !edge_ok(B, H, T) || !edge_cl_ok(y)) return TT_E_BADARG;
     int th, tt, n; edge_tiles(B, H, T, th, tt, n);
-    if (T % 4 == 0) hipLaunchKernelGGL((k_cin_fwd<true, 1>), dim3(edge_grid(n)), dim3(NT), 0, tt_stream(stream), x, w, b, (e16*)y, H, T, th, tt, n);
+    if (edge_vec(T, x)) hipLaunchKernelGGL((k_cin_fwd<true, 1>), dim3(edge_grid(n)), dim3(NT), 0, tt_stream(stream), x, w, b, (e16*)y, H, T, th, tt, n);
     else hipLaunchKernelGGL((k_cin_fwd<false, 1>), dim3(edge_grid(n)), dim3(NT), 0, tt_stream(stream), x, w, b, (e16*)y, H, T, th, tt, n);
     TT_LAUNCH_CHECK();
     return 0;
@@ -753,11 +758,11 @@ int tt_convin16_1_fwd(const float* x, const float* w, const float* b, void* y, i
 
 int tt_convin16_1_bwd(const float* x, const void* y, const void* dy, const float* w, float* dx, float* dw, float* db, void* ws, int B,
                       int H, int T, void* stream) {
-    if (!x || !dy || !w || !dw || !db || !ws || !edge_ok(B, H, T)) return TT_E_BADARG;       // y == NULL: dy is already gated
+    if (!x || !dy || !w || !dw || !db || !ws || !edge_ok(B, H, T) || !edge_cl_ok(y, dy)) return TT_E_BADARG;       // y == NULL: dy is already gated
     int th, tt, n; edge_tiles(B, H, T, th, tt, n);
     const int grid = edge_grid(n);
     hipStream_t st = tt_stream(stream);
-    const bool vec = T % 4 == 0;
+    const bool vec = edge_vec(T, x);
 #define CIN1_BWD(DX_, V_, P_) hipLaunchKernelGGL((k_cin_bwd<DX_, V_, P_, 1>), dim3(grid), dim3(NT), 0, st, x, (const e16*)y, (const e16*)dy, w, dx, (float*)ws, H, T, th, tt, n, tt_loss_unscale())
     if (y) {
         if (dx) { if (vec) CIN1_BWD(true, true, false); else CIN1_BWD(true, false, false); }
@@ -774,7 +779,7 @@ int tt_convin16_1_bwd(const float* x, const void* y, const void* dy, const float
 }
 
 int tt_convout16_1_fwd(const void* x, const float* w, const float* b, float* y, int B, int H, int T, int act, void* stream) {
-    if (!x || !w || !b || !y || !edge_ok(B, H, T)) return TT_E_BADARG;
+    if (!x || !w || !b || !y || !edge_ok(B, H, T) || !edge_cl_ok(x)) return TT_E_BADARG;
     int th, tt, n; edge_tiles(B, H, T, th, tt, n);
     hipStream_t st = tt_stream(stream);
     const dim3 grid(edge_grid(n));
@@ -788,14 +793,14 @@ int tt_convout16_1_fwd(const void* x, const float* w, const float* b, float* y, 
 
 int tt_convout16_1_bwd(const void* x, const float* y, const float* dy, const float* w, void* dx, float* dw, float* db, void* ws, int B, int H,
                        int T, int act, void* stream) {
-    if (!x || !dy || !w || !dx || !dw || !db || !ws || !edge_ok(B, H, T)) return TT_E_BADARG;
+    if (!x || !dy || !w || !dx || !dw || !db || !ws || !edge_ok(B, H, T) || !edge_cl_ok(x, dx)) return TT_E_BADARG;
     if ((act != TT_ACT_NONE && act != TT_ACT_RELU && act != TT_ACT_SIGMOID) || (act != TT_ACT_NONE && !y)) return TT_E_BADARG;
     int th, tt, n; edge_tiles(B, H, T, th, tt, n);
     const int grid = edge_grid(n);
     hipStream_t st = tt_stream(stream);
     const float s = tt_loss_scale();
 #define COUT1_BWD(V_, A_) hipLaunchKernelGGL((k_cout_bwd<V_, 1, A_>), dim3(grid), dim3(NT), 0, st, (const e16*)x, dy, w, (e16*)dx, (float*)ws, H, T, th, tt, n, s, y)
-    if (T % 4 == 0) {
+    if (edge_vec(T, dy, act == TT_ACT_NONE ? nullptr : y)) {
         if (act == TT_ACT_NONE) COUT1_BWD(true, TT_ACT_NONE); else if (act == TT_ACT_RELU) COUT1_BWD(true, TT_ACT_RELU); else COUT1_BWD(true, TT_ACT_SIGMOID);
     } else {
         if (act == TT_ACT_NONE) COUT1_BWD(false, TT_ACT_NONE); else if (act == TT_ACT_RELU) COUT1_BWD(false, TT_ACT_RELU); else COUT1_BWD(false, TT_ACT_SIGMOID);

@@ -1013,7 +1013,7 @@ int ttx_wide_rb_bwd_onepass(LevelCtx* ctx, const void* x, const void* h1, const 
                             void* stream) {
     if (!x || !h1 || !dy || !w1 || !w2 || !b2 || !dx || !dw1 || !db1 || !dw2 || !db2 || !ws) return TT_E_BADARG;
     if (C != 16 && C != 32) return TT_E_UNSUPPORTED;
-    if (!fshape_ok(B, C, H, T)) return TT_E_BADARG;
+    if (!fshape_ok(B, C, H, T) || !ptrs_aligned(16, x, h1, dy, dx, ws)) return TT_E_BADARG;
     const e16 *xi = (const e16*)x, *hi = (const e16*)h1, *gi = (const e16*)dy;
     hipStream_t st = tt_stream(stream);
     if (C == 16) return bwds_c<16>(xi, hi, gi, w1, w2, b2, (e16*)dx, dw1, db1, dw2, db2, (unsigned char*)ws, B, H, T, dilation, st, ctx);
@@ -1065,7 +1065,7 @@ int tt_wide_rb_bwd_fused(const void* x, const void* dy, const float* w1, const f
                          void* stream) {
     if (!x || !dy || !w1 || !b1 || !w2 || !b2 || !dx || !dw1 || !db1 || !dw2 || !db2 || !ws) return TT_E_BADARG;
     if (C != 16 && C != 32) return TT_E_UNSUPPORTED;
-    if (!fshape_ok(B, C, H, T)) return TT_E_BADARG;
+    if (!fshape_ok(B, C, H, T) || !ptrs_aligned(16, x, dy, dx, ws)) return TT_E_BADARG;
     const e16 *xi = (const e16*)x, *gi = (const e16*)dy;
     hipStream_t st = tt_stream(stream);
     if (C == 16) return fused_c<16>(xi, gi, w1, b1, w2, b2, (e16*)dx, dw1, db1, dw2, db2, (unsigned char*)ws, B, H, T, dilation, st);

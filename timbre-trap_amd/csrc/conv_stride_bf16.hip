@@ -957,6 +957,11 @@ int launch_w4(const e16* small, const e16* big, const e16* ygate, float* dw, flo
     return 0;
 }
 
+// The un-gated operand of k_w4 (both in the pregated forms) arrives by LDS-DMA, every other cl16 access is a 16-byte piece of a pixel
+// (8 bytes at C = 4, where T even keeps pixel pairs whole): cl16 pointers on 16-byte boundaries, tested before anything is launched.
+// w, b, dw, db and ws (fp32 partials) are reached by 4-byte accesses.
+template <class... P> inline bool stride_aligned(P... p) { return ptrs_aligned(16, p...); }
+
 inline bool ok_shape(int B, int C, int H, int T) {
     return B > 0 && H >= 4 && T > 0 && (C == 4 || C == 8 || C == 16 || C == 32) && (C != 4 || T % 2 == 0) &&
            (long)H * T * 2 * C < (1l << 31);
@@ -986,7 +991,7 @@ int64_t tt_stride16_scratch_bytes(int C) {
 }
 
 int tt_sconv16_fwd(const void* x, const float* w, const float* b, void* y, int B, int C, int H, int T, void* stream) {
-    if (!x || !w || !b || !y || !ok_shape(B, C, H, T)) return TT_E_BADARG;
+    if (!x || !w || !b || !y || !ok_shape(B, C, H, T) || !stride_aligned(x, y)) return TT_E_BADARG;
     const int Ho = (H - 4) / 2 + 1;
     hipStream_t st = tt_stream(stream);
     TT_BY_C(C, (launch_s4<CC, true>((const e16*)x, w, b, (e16*)y, B, H, Ho, T, st)));
@@ -994,7 +999,7 @@ int tt_sconv16_fwd(const void* x, const float* w, const float* b, void* y, int B
 
 int tt_sconv16_bwd(const void* x, const void* y, const void* dy, const float* w, void* dx, float* dw, float* db, void* ws, int B,
                    int C, int H, int T, void* stream) {
-    if (!x || !y || !dy || !w || !dw || !db || !ws || !ok_shape(B, C, H, T)) return TT_E_BADARG;
+    if (!x || !y || !dy || !w || !dw || !db || !ws || !ok_shape(B, C, H, T) || !stride_aligned(x, y, dy, dx)) return TT_E_BADARG;
     const int Ho = (H - 4) / 2 + 1;
     hipStream_t st = tt_stream(stream);
     // the data gradient rides along in the weight-gradient pass where the registers allow it: one pass for weight, bias and data gradient
@@ -1011,7 +1016,7 @@ int tt_sconv16_bwd(const void* x, const void* y, const void* dy, const float* w,
 }
 
 int tt_tconv16_fwd(const void* x, const float* w, const float* b, void* y, int B, int C, int H, int T, int out_pad, void* stream) {
-    if (!x || !w || !b || !y || B <= 0 || H <= 0 || T <= 0 || out_pad < 0 || out_pad > 1) return TT_E_BADARG;
+    if (!x || !w || !b || !y || B <= 0 || H <= 0 || T <= 0 || out_pad < 0 || out_pad > 1 || !stride_aligned(x, y)) return TT_E_BADARG;
     const int Ho = 2 * H + 2 + out_pad;
     if (!ok_shape(B, C, Ho, T)) return TT_E_BADARG;
     hipStream_t st = tt_stream(stream);
@@ -1020,7 +1025,7 @@ int tt_tconv16_fwd(const void* x, const float* w, const float* b, void* y, int B
 
 int tt_tconv16_bwd(const void* x, const void* y, const void* dy, const float* w, void* dx, float* dw, float* db, void* ws, int B,
                    int C, int H, int T, int out_pad, void* stream) {
-    if (!x || !y || !dy || !w || !dw || !db || !ws || B <= 0 || H <= 0 || T <= 0 || out_pad < 0 || out_pad > 1) return TT_E_BADARG;
+    if (!x || !y || !dy || !w || !dw || !db || !ws || B <= 0 || H <= 0 || T <= 0 || out_pad < 0 || out_pad > 1 || !stride_aligned(x, y, dy, dx)) return TT_E_BADARG;
     const int Ho = 2 * H + 2 + out_pad;
     if (!ok_shape(B, C, Ho, T)) return TT_E_BADARG;
     hipStream_t st = tt_stream(stream);
@@ -1032,7 +1037,7 @@ int tt_tconv16_bwd(const void* x, const void* y, const void* dy, const float* w,
 // The same two backward passes with dy ALREADY gated (g = dy * ELU'(y), as tt_wide_level_bwd_gated leaves it): y is not read.
 int tt_sconv16_bwd_pregated(const void* x, const void* g, const float* w, void* dx, float* dw, float* db, void* ws, int B, int C, int H,
                             int T, void* stream) {
-    if (!x || !g || !w || !dw || !db || !ws || !ok_shape(B, C, H, T)) return TT_E_BADARG;
+    if (!x || !g || !w || !dw || !db || !ws || !ok_shape(B, C, H, T) || !stride_aligned(x, g, dx)) return TT_E_BADARG;
     const int Ho = (H - 4) / 2 + 1;
     hipStream_t st = tt_stream(stream);
     if (dx) { TT_BY_C(C, (launch_w4<CC, true, true, true>((const e16*)g, (const e16*)x, nullptr, dw, db, (float*)ws, w, (e16*)dx, B, Ho, H, T, st))); }
@@ -1041,7 +1046,7 @@ int tt_sconv16_bwd_pregated(const void* x, const void* g, const float* w, void* 
 
 int tt_tconv16_bwd_pregated(const void* x, const void* g, const float* w, void* dx, float* dw, float* db, void* ws, int B, int C, int H,
                             int T, int out_pad, int gate_dx, void* stream) {
-    if (!x || !g || !w || !dw || !db || !ws || B <= 0 || H <= 0 || T <= 0 || out_pad < 0 || out_pad > 1 || (gate_dx && !dx)) return TT_E_BADARG;
+    if (!x || !g || !w || !dw || !db || !ws || B <= 0 || H <= 0 || T <= 0 || out_pad < 0 || out_pad > 1 || (gate_dx && !dx) || !stride_aligned(x, g, dx)) return TT_E_BADARG;
     const int Ho = 2 * H + 2 + out_pad;
     if (!ok_shape(B, C, Ho, T)) return TT_E_BADARG;
     hipStream_t st = tt_stream(stream);

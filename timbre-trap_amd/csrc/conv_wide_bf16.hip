@@ -1523,6 +1523,7 @@ int64_t tt_wide_scratch_bytes(int B, int C, int H, int T) {
 
 int tt_wide_pack(const float* x, void* out, int B, int C, int H, int T, void* stream) {
     if (!x || !out || !(shape_ok(B, C, H, T) || (C == 64 && B > 0 && H > 0 && T > 0))) return TT_E_BADARG;
+    if (!ptrs_aligned(16, out)) return TT_E_BADARG;              // the cl16 side moves in 16-byte pieces; x by 4-byte loads
     const long npix = (long)B * H * T, pieces = npix * C / 8;
     const unsigned grid = (unsigned)((pieces + NT - 1) / NT);
     hipStream_t st = tt_stream(stream);
@@ -1539,6 +1540,7 @@ int tt_wide_pack(const float* x, void* out, int B, int C, int H, int T, void* st
 
 int tt_wide_unpack(const void* in, float* y, int B, int C, int H, int T, void* stream) {
     if (!in || !y || !(shape_ok(B, C, H, T) || (C == 64 && B > 0 && H > 0 && T > 0))) return TT_E_BADARG;
+    if (!ptrs_aligned(16, in)) return TT_E_BADARG;               // 16-byte pieces of the cl16 side; y by 4-byte stores
     const long npix = (long)B * H * T, pieces = npix * C / 8;
     const unsigned grid = (unsigned)((pieces + NT - 1) / NT);
     hipStream_t st = tt_stream(stream);
@@ -1556,6 +1558,7 @@ int tt_wide_unpack(const void* in, float* y, int B, int C, int H, int T, void* s
 int tt_wide_rb_fwd(const void* x, const float* w1, const float* b1, const float* w2, const float* b2, void* y, void* h1, int B,
                    int C, int H, int T, int dilation, void* stream) {
     if (!x || !w1 || !b1 || !w2 || !b2 || !y || !shape_ok(B, C, H, T)) return TT_E_BADARG;
+    if (!ptrs_aligned(16, x, y, h1)) return TT_E_BADARG;         // x by LDS-DMA, y and h1 in 16-byte pieces
     const e16* xi = (const e16*)x;
     e16 *yo = (e16*)y, *ho = (e16*)h1;
     hipStream_t st = tt_stream(stream);
@@ -1571,7 +1574,7 @@ int tt_wide_rb_fwd_join(const void* x, const float* w1, const float* b1, const f
                         const void* skip, const float* skip_weights, int skip_idx, int skip_B, int B, int C, int H, int T, int dilation,
                         void* stream) {
     if (!x || !w1 || !b1 || !w2 || !b2 || !y || !skip || skip_idx < 0 || skip_B < 1 || B % skip_B || !shape_ok(B, C, H, T)) return TT_E_BADARG;
-    if (y == skip || y == x) return TT_E_BADARG;
+    if (y == skip || y == x || !ptrs_aligned(16, x, y, h1, skip)) return TT_E_BADARG;
     const e16 *xi = (const e16*)x, *je = (const e16*)skip;
     const float* jw = skip_weights ? skip_weights + skip_idx : nullptr;
     e16 *yo = (e16*)y, *ho = (e16*)h1;
@@ -1621,6 +1624,9 @@ static int rb_bwd(LevelCtx* ctx, const void* x, const void* h1, const void* dy, 
                   float* dw1, float* db1, float* dw2, float* db2, void* ws, int B, int C, int H, int T, int dilation, void* stream) {
     if (!x || !h1 || !dy || !w1 || !w2 || !b2 || !dx || !dw1 || !db1 || !dw2 || !db2 || !ws || !shape_ok(B, C, H, T))
         return TT_E_BADARG;
+    // x, h1, dy by LDS-DMA, dx in 16-byte pieces; ws: at C = 32 its dA1 region is read back by LDS-DMA, at C = 4, 8, 16 it holds fp32
+    // partials only (4-byte accesses) -- 16 bytes are asked of it at every width so that the contract is one rule (include/ttrap.h)
+    if (!ptrs_aligned(16, x, h1, dy, dx, ws)) return TT_E_BADARG;
     const e16 *xi = (const e16*)x, *hi = (const e16*)h1, *gi = (const e16*)dy;
     e16* go = (e16*)dx;
     unsigned char* w = (unsigned char*)ws;
@@ -1654,6 +1660,10 @@ static int level_bwd(int gate, const SkipJ& skip, int nblocks, const void* const
     if (nblocks < 1 || nblocks > 4 || !x || !h1 || !dy || !w1 || !w2 || !b2 || !dx || !dw1 || !db1 || !dw2 || !db2 || !ws || !dilations ||
         (nblocks > 1 && (!tmp0 || !tmp1)) || !shape_ok(B, C, H, T))
         return TT_E_BADARG;
+    // every block's tensors before the first launch (the weight images below): the per-block calls would find a misaligned one too late
+    if (!ptrs_aligned(16, dy, dx, tmp0, tmp1, ws, skip.g)) return TT_E_BADARG;
+    for (int i = 0; i < nblocks; ++i)
+        if (!x[i] || !h1[i] || !ptrs_aligned(16, x[i], h1[i])) return TT_E_BADARG;
     const int64_t one = (tt_wide_scratch_bytes(B, C, H, T) + 255) / 256 * 256;
     RedBatch batch;
     LevelCtx ctx;
@@ -1704,7 +1714,7 @@ static int level_bwd(int gate, const SkipJ& skip, int nblocks, const void* const
 }
 
 int tt_gate16(void* g, const void* y, int64_t n, void* stream) {
-    if (!g || !y || n < 0 || n % 8) return TT_E_BADARG;
+    if (!g || !y || n < 0 || n % 8 || !ptrs_aligned(16, g, y)) return TT_E_BADARG;        // 16-byte accesses
     if (n == 0) return 0;
     const long n8 = n / 8, want = (n8 + 255) / 256, cap = (long)8 * tt_cus();
     hipLaunchKernelGGL(k_gate_dx, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, tt_stream(stream), (e16*)g, (const e16*)y, n8);

@@ -489,6 +489,11 @@ int run_wgrad(const float* z, int Dz, float fill, const e16* g_in, const e16* gy
     return 0;
 }
 
+// Every cl16 tensor is read or written in 16-byte pieces of a pixel's channels, g of the weight gradient and the operands prepared in ws
+// by LDS-DMA (16 bytes per lane): cl16 pointers and ws on 16-byte boundaries, tested before anything is launched.  z, w, bias, out (fp32),
+// dw and db are reached by 4-byte accesses only.
+template <class... P> inline bool lat_aligned(P... p) { return ptrs_aligned(16, p...); }
+
 inline int cfg_of(int CT, int D) {                               // 1: CT 32, D <= 48;  2: CT 64, D <= 144;  0: unsupported
     if (CT == 32 && D >= 1 && D <= 48) return 1;
     if (CT == 64 && D >= 1 && D <= 144) return 2;
@@ -513,6 +518,7 @@ int64_t tt_latent16_scratch_bytes(int B, int CT, int D, int E, int T) {
 int tt_latent16_contract(const void* in, const void* gy, const float* w, const float* bias, float* out, void* ws, int B, int CT, int D,
                          int Dout, int E, int T, void* stream) {
     if (!in || !w || !out || !ws || B <= 0 || E <= 0 || T <= 0 || T % 16 || Dout < 1 || Dout > D) return TT_E_BADARG;
+    if (!lat_aligned(in, gy, ws)) return TT_E_BADARG;
     hipStream_t st = tt_stream(stream);
     const e16 *i = (const e16*)in, *y = (const e16*)gy;
     unsigned char* s = (unsigned char*)ws;
@@ -528,6 +534,7 @@ int tt_latent16_contract(const void* in, const void* gy, const float* w, const f
 int tt_latent16_expand(const float* z, int Dz, float fill, const float* w, const float* bias, void* out, void* ws, int B, int CT, int D,
                        int E, int T, void* stream) {
     if (!z || !w || !out || !ws || B <= 0 || E <= 0 || T <= 0 || T % 16 || (Dz != D && Dz != D - 1)) return TT_E_BADARG;
+    if (!lat_aligned(out, ws)) return TT_E_BADARG;
     hipStream_t st = tt_stream(stream);
     e16* o = (e16*)out;
     unsigned char* s = (unsigned char*)ws;
@@ -542,6 +549,7 @@ int tt_latent16_expand(const float* z, int Dz, float fill, const float* w, const
 int tt_latent16_wgrad(const float* z, int Dz, float fill, const void* g, const void* gy, float* dw, float* db, void* ws, int B, int CT,
                       int D, int E, int T, void* stream) {
     if (!z || !g || !dw || !ws || (gy && !db) || B <= 0 || E <= 0 || T <= 0 || T % 16 || (Dz != D && Dz != D - 1)) return TT_E_BADARG;
+    if (!lat_aligned(g, gy, ws)) return TT_E_BADARG;
     hipStream_t st = tt_stream(stream);
     const e16 *gi = (const e16*)g, *y = (const e16*)gy;
     unsigned char* s = (unsigned char*)ws;
@@ -570,7 +578,7 @@ int tt_latent16_pregated_ok(int CT, int D) {
 
 int tt_latent16_expand_gated(const float* z, const float* w, const void* gy, void* out, void* ws, int B, int CT, int D, int E, int T,
                              void* stream) {
-    if (!z || !w || !gy || !out || !ws || B <= 0 || E <= 0 || T <= 0 || T % 16) return TT_E_BADARG;
+    if (!z || !w || !gy || !out || !ws || B <= 0 || E <= 0 || T <= 0 || T % 16 || !lat_aligned(gy, out, ws)) return TT_E_BADARG;
     hipStream_t st = tt_stream(stream);
     switch (cfg_of(CT, D)) {
         case 1: return run_expand<32, 3, 2, false, true>(z, D, 0.f, w, nullptr, (e16*)out, (unsigned char*)ws, B, D, E, T, st, (const e16*)gy);
@@ -581,9 +589,13 @@ int tt_latent16_expand_gated(const float* z, const float* w, const void* gy, voi
 
 int tt_latent16_contract_pregated(const void* g, const float* w, float* out, void* ws, int B, int CT, int D, int Dout, int E, int T,
                                   void* stream) {
-    if (!g || !w || !out || !ws || B <= 0 || E <= 0 || T <= 0 || T % 16 || Dout < 1 || Dout > D) return TT_E_BADARG;
+    if (!g || !w || !out || !ws || B <= 0 || E <= 0 || T <= 0 || T % 16 || Dout < 1 || Dout > D || !lat_aligned(g, ws)) return TT_E_BADARG;
     hipStream_t st = tt_stream(stream);
-    switch (cfg_of(CT, D)) {
+    // the pair is one backward: where the weight gradient has no free row for the bias gradient (tt_latent16_pregated_ok == 0) no caller may
+    // have promised the gate, and this half refuses as the header says (it used to run)
+    const int cfg = cfg_of(CT, D);
+    if ((cfg == 1 && D >= 16 * 3) || (cfg == 2 && D >= 16 * 9)) return TT_E_UNSUPPORTED;
+    switch (cfg) {
         case 1: return run_contract<32, 3, 2, false>((const e16*)g, nullptr, w, nullptr, out, (unsigned char*)ws, B, D, Dout, E, T, st, true);
         case 2: return run_contract<64, 9, 5, false>((const e16*)g, nullptr, w, nullptr, out, (unsigned char*)ws, B, D, Dout, E, T, st, true);
     }
@@ -592,7 +604,7 @@ int tt_latent16_contract_pregated(const void* g, const float* w, float* out, voi
 
 int tt_latent16_wgrad_pregated(const float* z, int Dz, float fill, const void* g, float* dw, float* db, void* ws, int B, int CT, int D,
                                int E, int T, void* stream) {
-    if (!z || !g || !dw || !db || !ws || B <= 0 || E <= 0 || T <= 0 || T % 16 || (Dz != D && Dz != D - 1)) return TT_E_BADARG;
+    if (!z || !g || !dw || !db || !ws || B <= 0 || E <= 0 || T <= 0 || T % 16 || (Dz != D && Dz != D - 1) || !lat_aligned(g, ws)) return TT_E_BADARG;
     hipStream_t st = tt_stream(stream);
     switch (cfg_of(CT, D)) {
         case 1: return run_wgrad<32, 3, 2, false>(z, Dz, fill, (const e16*)g, nullptr, dw, db, (unsigned char*)ws, B, D, E, T, st, true);
