@@ -842,12 +842,21 @@ int tt_resample_normalize(float* y, int B, int64_t Lout, const float* peak_parti
  * tt_x3_rb_fwd / tt_x3_level_fwd save no hidden activation: the no-grad path of ops.residual_level in fp32 mode.  The chain, strided and latent
  * entries below are forward only; the block has a training forward and a backward further down (tt_x3_rb_fwd_train / tt_x3_rb_bwd).
  *   tt_x3_bytes      bytes of one activation tensor in the x3 layout [B][H][T][2][C] halves (= B C H T 4)
- *   tt_x3_pack       x (B,C,H,T) fp32 planar -> x3              tt_x3_unpack   the inverse (exact to 2^-23 relative)
+ *   tt_x3_pack       x (B,C,H,T) fp32 planar -> x3              tt_x3_unpack   the inverse.  A pair holds v to max(2^-23 |v|, 2^-36):
+ *                    2^-23 relative from |v| = 2^-13 upwards, absolute below (derivation: tests/x3_ref.py); the join is exact in fp32
  *   tt_x3_rb_fwd     y = ELU(W2 . ELU(W1 (*)_dil x + b1) + b2) + x; x is an x3 tensor, y an x3 tensor (planar_out = 0; x != y) or an
  *                    fp32 planar (B,C,H,T) tensor (planar_out = 1); weights fp32 (C,C,3,3) / (C,C,1,1)
  *   tt_x3_level_fwd  nblocks blocks (w1[i], b1[i], w2[i], b2[i], dilations[i]); x is fp32 planar (x3_in = 0: packed first) or an x3
  *                    tensor, y fp32 planar (x3_out = 0: written by the last block directly) or an x3 tensor;
- *                    ws = tt_x3_level_scratch_bytes bytes */
+ *                    ws = tt_x3_level_scratch_bytes bytes; x3_in with y == x (in place): TT_E_BADARG at every nblocks
+ * Alignment (every entry point of csrc/conv_x3.hip, the training, strided and latent ones below included): an x3 / x3n tensor is read by
+ * 16-byte LDS-DMA or in 8- / 16-byte pieces and written in 8- / 16-byte pieces, and so is the head of every ws -- each such pointer must be
+ * a multiple of 16 bytes, else TT_E_BADARG before anything is launched (the level entries test all of theirs up front):
+ *   tt_x3_pack[_scaled] out; tt_x3_unpack[_scaled] in; tt_x3_rb_fwd x, y (x3); tt_x3_rb_fwd_train x, h1, y (x3); tt_x3_rb_bwd x, h1, dy, ws,
+ *   dx (x3); tt_x3_level_fwd ws, x (x3_in), y (x3_out); tt_x3n_rb_fwd x (planar_in = 0), y (planar_out = 0); tt_x3n_level_fwd ws;
+ *   tt_x3_sconv_fwd / tt_x3_tconv_fwd x (planar_in = 0), y (planar_out = 0); tt_x3_latent_encode x, ws; tt_x3_latent_decode ws, y (x3).
+ * fp32 planar tensors, weights, biases, scale, the four gradients and the arguments of tt_x3_grad_scale are reached by 4-byte accesses:
+ * any float pointer. */
 int64_t tt_x3_bytes(int B, int C, int H, int T);
 int64_t tt_x3_level_scratch_bytes(int B, int C, int H, int T);
 
@@ -877,8 +886,9 @@ int tt_x3_level_fwd(int nblocks, const void* x, int x3_in, void* y, int x3_out, 
  * tensors (x, h1, y, dy, dx) are x3 tensors of tt_x3_bytes bytes.
  *   tt_x3_rb_fwd_train  tt_x3_rb_fwd that also stores h1 = ELU(W1 (*)_dil x + b1) as an x3 tensor (x, y, h1 distinct)
  *   tt_x3_grad_scale    scale[0] = S, scale[1] = 1 / S (device memory, no host sync): the power of two that puts abs-max(dy[0..n)) into
- *                       [2^8, 2^9); S = 1 for an all-zero or a non-finite dy.  A pair of halves is exact to 2^-22 relative only above
- *                       ~2^-15, and activation gradients of a mean-reduced loss sit at 1e-7 .. 1e-10: every x3 GRADIENT tensor carries S.
+ *                       [2^8, 2^9) (exponent clamped to +-120); S = 1 for an all-zero or a non-finite dy.  A pair of halves is exact to
+ *                       2^-23 relative only from 2^-13 upwards (2^-36 absolute below), and activation gradients of a mean-reduced loss sit
+ *                       at 1e-7 .. 1e-10: every x3 GRADIENT tensor carries S.
  *                       ws: tt_x3_grad_scale_scratch_bytes() bytes
  *   tt_x3_pack_scaled   x3 = split(x * scale[0])            tt_x3_unpack_scaled   y = join(x3) * scale[1]   (scale = NULL: tt_x3_pack / _unpack)
  *   tt_x3_rb_bwd        reads what tt_resblock_bwd reads -- the block input x, h1 and the incoming gradient dy (x3, carrying S):

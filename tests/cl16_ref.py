@@ -161,9 +161,9 @@ class Arena:
             owner = [n for n, w in self.win.items() if w['start'] <= i < w['start'] + w['nbytes']]
             raise AssertionError('%s: a refused call wrote byte %d of the buffer (%s)' % (what, i, owner[0] if owner else 'a guard band'))
 
-    def verify(self, what):
+    def verify(self, what, finite=True):
         """Every byte outside the out / acc / scratch windows is unchanged (guard bands, inputs); every out element was written; out and acc
-        are finite."""
+        are finite (finite=False: a case whose outputs are non-finite by design keeps the other checks)."""
         if self.dev.is_cuda:
             torch.cuda.synchronize()
         same = (self.dev == self.before) | self.inside
@@ -182,7 +182,7 @@ class Arena:
                 if bool(untouched.any()):
                     raise AssertionError('%s: output %s was not written everywhere (element %d of %d still holds the fill)' % (
                         what, name, int(untouched.nonzero()[0]), raw.size(0)))
-            if w['kind'] in ('out', 'acc') and not bool(torch.isfinite(self.view(name)).all()):
+            if finite and w['kind'] in ('out', 'acc') and not bool(torch.isfinite(self.view(name)).all()):
                 raise AssertionError('%s: non-finite element in %s' % (what, name))
 
 

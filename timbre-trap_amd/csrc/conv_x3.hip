@@ -1301,7 +1301,7 @@ int launch_latdec(const float* z, int Dz, float fill, const float* w, const floa
 // accumulators; bias sums, ELU' and the residual add are fp32.  The weight and bias gradients leave every workgroup as a register dump
 // and k_x3_reduce sums the dumps in a fixed order (no float atomics: the backward is bit-reproducible) into the fp32 gradients (+=).
 //
-// Gradient range.  A (hi, lo) pair is exact to 2^-22 relative only while |v| >~ 2^-15 (below, it holds 2^-35 absolute), and activation
+// Gradient range.  A (hi, lo) pair is exact to 2^-23 relative only while |v| >= 2^-13 (below, it holds 2^-36 absolute), and activation
 // gradients of a mean-reduced loss sit at 1e-7 .. 1e-10.  The level's incoming dy is therefore multiplied by a power of two S, chosen on
 // the device (k_x3_absmax + k_x3_scale_fin: no host sync) so that abs-max(dy) S lies in [2^8, 2^9) -- 2^7 of headroom below 65504 for the
 // growth through the blocks of a level; S = 1 for an all-zero or a non-finite dy (the latter comes out non-finite by itself).  Every x3
@@ -1757,6 +1757,7 @@ int64_t tt_x3_bytes(int B, int C, int H, int T) {
 
 int tt_x3_pack_scaled(const float* x, void* out, const float* scale, int B, int C, int H, int T, void* stream) {
     if (!x || !out || !x3_layout_ok(B, C, H, T)) return TT_E_BADARG;
+    if (!ptrs_aligned(16, out)) return TT_E_BADARG;              // the x3 side moves in 16-byte pieces; x and scale by 4-byte loads
     const long npix = (long)B * H * T, pieces = npix * C / 8;
     const unsigned grid = (unsigned)((pieces + NT - 1) / NT);
     hipStream_t st = tt_stream(stream);
@@ -1773,6 +1774,7 @@ int tt_x3_pack(const float* x, void* out, int B, int C, int H, int T, void* stre
 
 int tt_x3_unpack_scaled(const void* in, float* y, const float* scale, int B, int C, int H, int T, void* stream) {
     if (!in || !y || !x3_layout_ok(B, C, H, T)) return TT_E_BADARG;
+    if (!ptrs_aligned(16, in)) return TT_E_BADARG;               // 16-byte pieces of the x3 side; y by 4-byte stores
     const long npix = (long)B * H * T, pieces = npix * C / 8;
     const unsigned grid = (unsigned)((pieces + NT - 1) / NT);
     hipStream_t st = tt_stream(stream);
@@ -1790,12 +1792,14 @@ int tt_x3_unpack(const void* in, float* y, int B, int C, int H, int T, void* str
 int tt_x3_rb_fwd(const void* x, const float* w1, const float* b1, const float* w2, const float* b2, void* y, int planar_out, int B,
                  int C, int H, int T, int dilation, void* stream) {
     if (!x || !w1 || !b1 || !w2 || !b2 || !y || x == y || !x3_shape_ok(B, C, H, T)) return TT_E_BADARG;
+    if (!ptrs_aligned(16, x) || (!planar_out && !ptrs_aligned(16, y))) return TT_E_BADARG;   // x by LDS-DMA, an x3 y in 8- / 16-byte pieces
     return x3_block((const e16*)x, w1, b1, w2, b2, y, planar_out != 0, B, C, H, T, dilation, tt_stream(stream));
 }
 
 int tt_x3_rb_fwd_train(const void* x, const float* w1, const float* b1, const float* w2, const float* b2, void* y, int planar_out, void* h1,
                        int B, int C, int H, int T, int dilation, void* stream) {
     if (!x || !w1 || !b1 || !w2 || !b2 || !y || !h1 || x == y || x == h1 || y == h1 || !x3_shape_ok(B, C, H, T)) return TT_E_BADARG;
+    if (!ptrs_aligned(16, x, h1) || (!planar_out && !ptrs_aligned(16, y))) return TT_E_BADARG;
     hipStream_t st = tt_stream(stream);
     X3Aux aux;
     aux.h1 = static_cast<e16*>(h1);
@@ -1832,6 +1836,8 @@ int tt_x3_rb_bwd(const void* x, const void* h1, const void* dy, const float* w1,
     if (!x || !h1 || !dy || !w1 || !w2 || !b2 || !dw1 || !db1 || !dw2 || !db2 || !scale || !ws || (dx && (dx == dy || dx == x || dx == h1)) ||
         !x3_shape_ok(B, C, H, T) || (int64_t)B * H * T >= ((int64_t)1 << 34) || dilation < 1 || dilation > 3)
         return TT_E_BADARG;
+    // x and the g1 region at the head of ws by LDS-DMA, h1 / dy / an x3 dx in 8- / 16-byte pieces; everything else by 4-byte accesses
+    if (!ptrs_aligned(16, x, h1, dy, ws) || (!planar_dx && !ptrs_aligned(16, dx))) return TT_E_BADARG;
     hipStream_t st = tt_stream(stream);
     const e16 *xe = static_cast<const e16*>(x), *he = static_cast<const e16*>(h1), *de = static_cast<const e16*>(dy);
     unsigned char* w = static_cast<unsigned char*>(ws);
@@ -1845,6 +1851,11 @@ int tt_x3_level_fwd(int nblocks, const void* x, int x3_in, void* y, int x3_out, 
     if (nblocks < 1 || !x || !y || !w1 || !b1 || !w2 || !b2 || !dilations || !ws || !x3_shape_ok(B, C, H, T)) return TT_E_BADARG;
     for (int i = 0; i < nblocks; ++i)
         if (!w1[i] || !b1[i] || !w2[i] || !b2[i] || dilations[i] < 1 || dilations[i] > 3) return TT_E_BADARG;
+    // every block's x3 operand is x, y or one of the two halves of ws (256-byte multiples apart): all tested here, before the first launch
+    if (!ptrs_aligned(16, ws) || (x3_in && !ptrs_aligned(16, x)) || (x3_out && !ptrs_aligned(16, y))) return TT_E_BADARG;
+    // in place (x3_in with y == x): refused by contract at every nblocks.  One block would write what it reads; with two or more the last
+    // block reads a half of ws, which happened to work and was accepted before the contract was written down
+    if (x3_in && y == x) return TT_E_BADARG;
     const int64_t bytes = tt_x3_bytes(B, C, H, T);
     unsigned char* buf[2] = {static_cast<unsigned char*>(ws), static_cast<unsigned char*>(ws) + ((bytes + 255) / 256) * 256};
     const void* cur = x;
@@ -1855,7 +1866,6 @@ int tt_x3_level_fwd(int nblocks, const void* x, int x3_in, void* y, int x3_out, 
     for (int i = 0; i < nblocks; ++i) {                          // the last block writes into y: x3, or fp32 planar straight away
         const bool last = i == nblocks - 1;
         void* dst = last ? y : (cur == buf[0] ? buf[1] : buf[0]);
-        if (dst == cur) return TT_E_BADARG;                      // x3_in with y == x
         if (int rc = tt_x3_rb_fwd(cur, w1[i], b1[i], w2[i], b2[i], dst, last && !x3_out, B, C, H, T, dilations[i], stream)) return rc;
         cur = dst;
     }
@@ -1865,6 +1875,7 @@ int tt_x3_level_fwd(int nblocks, const void* x, int x3_in, void* y, int x3_out, 
 int tt_x3_sconv_fwd(const void* x, int planar_in, const float* w, const float* bias, void* y, int planar_out, int B, int C, int H, int T,
                     void* stream) {
     if (!x || !w || !bias || !y || B <= 0 || T <= 0 || H < 4) return TT_E_BADARG;
+    if ((!planar_in && !ptrs_aligned(16, x)) || (!planar_out && !ptrs_aligned(16, y))) return TT_E_BADARG;      // x3 tensors: 8- / 16-byte pieces
     const int Hout = (H - 4) / 2 + 1;
     hipStream_t st = tt_stream(stream);
     if (planar_in) return C == 8 ? launch_x3s<8, false, true>(x, w, bias, y, planar_out, B, H, Hout, T, st) : TT_E_UNSUPPORTED;
@@ -1876,6 +1887,7 @@ int tt_x3_sconv_fwd(const void* x, int planar_in, const float* w, const float* b
 int tt_x3_tconv_fwd(const void* x, int planar_in, const float* w, const float* bias, void* y, int planar_out, int B, int C, int H, int T,
                     int out_pad, void* stream) {
     if (!x || !w || !bias || !y || B <= 0 || H <= 0 || T <= 0 || (out_pad != 0 && out_pad != 1)) return TT_E_BADARG;
+    if ((!planar_in && !ptrs_aligned(16, x)) || (!planar_out && !ptrs_aligned(16, y))) return TT_E_BADARG;
     const int Hout = 2 * H + 2 + out_pad;                        // C = output channels; the input has 2 C
     hipStream_t st = tt_stream(stream);
     if (planar_in) return C == 32 ? launch_x3s<64, true, true>(x, w, bias, y, planar_out, B, H, Hout, T, st) : TT_E_UNSUPPORTED;
@@ -1892,6 +1904,7 @@ int64_t tt_x3_latent_scratch_bytes(int C, int E, int D) {
 int tt_x3_latent_encode(const void* x, const float* w, const float* bias, float* z, void* ws, int B, int C, int E, int D, int T,
                         void* stream) {
     if (!x || !w || !z || !ws || B <= 0 || E <= 0 || T <= 0) return TT_E_BADARG;
+    if (!ptrs_aligned(16, x, ws)) return TT_E_BADARG;            // x in 16-byte pieces; the weight image in ws by 16-byte stores and LDS-DMA
     hipStream_t st = tt_stream(stream);
     if (C == 64 && D == 128) return launch_latenc<64, 128>((const e16*)x, w, bias, z, (unsigned char*)ws, B, E, T, st);
     if (C == 32 && D == 32) return launch_latenc<32, 32>((const e16*)x, w, bias, z, (unsigned char*)ws, B, E, T, st);
@@ -1901,6 +1914,7 @@ int tt_x3_latent_encode(const void* x, const float* w, const float* bias, float*
 int tt_x3_latent_decode(const float* z, int Dz, float fill, const float* w, const float* bias, void* y, int planar_out, void* ws, int B,
                         int C, int E, int D, int T, void* stream) {
     if (!z || !w || !y || !ws || B <= 0 || E <= 0 || T <= 0 || (Dz != D && Dz != D + 1)) return TT_E_BADARG;
+    if (!ptrs_aligned(16, ws) || (!planar_out && !ptrs_aligned(16, y))) return TT_E_BADARG;
     if ((int64_t)E * C * 4 + 2 * (int64_t)(D / 32) * (C / 16) * 2048 > 160 * 1024) return TT_E_UNSUPPORTED;
     hipStream_t st = tt_stream(stream);
     if (C == 64 && D == 128) return launch_latdec<64, 128>(z, Dz, fill, w, bias, y, planar_out != 0, (unsigned char*)ws, B, E, T, st);
@@ -1922,6 +1936,7 @@ int64_t tt_x3n_level_scratch_bytes(int B, int C, int H, int T) {
 int tt_x3n_rb_fwd(const void* x, int planar_in, const float* w1, const float* b1, const float* w2, const float* b2, void* y, int planar_out,
                   int B, int C, int H, int T, int dilation, void* stream) {
     if (!x || !w1 || !b1 || !w2 || !b2 || !y || x == y || !x3n_shape_ok(B, C, H, T)) return TT_E_BADARG;
+    if ((!planar_in && !ptrs_aligned(16, x)) || (!planar_out && !ptrs_aligned(16, y))) return TT_E_BADARG;      // x3n: LDS-DMA in, 8- / 16-byte pieces out
     hipStream_t st = tt_stream(stream);
     return C == 4 ? x3n_d<4>(x, planar_in != 0, w1, b1, w2, b2, y, planar_out != 0, B, H, T, dilation, st)
                   : x3n_d<8>(x, planar_in != 0, w1, b1, w2, b2, y, planar_out != 0, B, H, T, dilation, st);
@@ -1932,6 +1947,7 @@ int tt_x3n_level_fwd(int nblocks, const float* x, float* y, const float* const* 
     if (nblocks < 1 || !x || !y || !w1 || !b1 || !w2 || !b2 || !dilations || !ws || !x3n_shape_ok(B, C, H, T)) return TT_E_BADARG;
     for (int i = 0; i < nblocks; ++i)
         if (!w1[i] || !b1[i] || !w2[i] || !b2[i] || dilations[i] < 1 || dilations[i] > 3) return TT_E_BADARG;
+    if (!ptrs_aligned(16, ws)) return TT_E_BADARG;               // both halves of ws hold x3n tensors (256-byte multiples apart)
     const int64_t bytes = (int64_t)B * H * T * C * 4;
     unsigned char* buf[2] = {static_cast<unsigned char*>(ws), static_cast<unsigned char*>(ws) + ((bytes + 255) / 256) * 256};
     const void* cur = x;
