@@ -165,6 +165,28 @@ int tt_cqt_generic_forward_bwd(const tt_cqt_gplan* plan, const float* dcoeffs, f
 int tt_cqt_generic_inverse_bwd(const tt_cqt_gplan* plan, const float* daudio, float* dcoeffs, void* scratch,
                                int B, int n_blocks, int out_complex, void* stream);
 
+/* Phase retrieval for the magnitude variants (version 20): audio from |c| by the Griffin-Lim iteration with the momentum of "fast
+ * Griffin-Lim" (Perraudin, Balazs, Sondergaard 2013).  The reference has no counterpart: TimbreTrapMag / TimbreTrapMagDB
+ * (modules.py:892-1075) return magnitudes, CQT.decode (cqtwrapper.py:184-213) needs complex coefficients, and experiments/sonify.py:109
+ * / :158 (audio_rec = model.sliCQ.decode(reconstruction)) therefore serves the complex model only; this entry is the way back for the
+ * other two, under the same inf-norm (cqtwrapper.py:209-211).
+ *   mag (B, 1, F, n_blocks*1024) target magnitudes, taken as given (no clamp, no non-finite guard)
+ *   audio_init (B, 1, n_blocks*66150) the start x_0 (e.g. the input mixture: "mixture phase"), never written; NULL = silence
+ * Iteration k = 0 .. n_iter-1, all enqueued by the one call with no host synchronisation:
+ *   c = analysis(x_k);  p = mag c / |c|, and mag + 0i where |c| == 0 (a silent start is the zero-phase synthesis; no 0 / 0);
+ *   y_k = synthesis(p);  x_{k+1} = y_k + momentum (y_k - y_{k-1}),  x_1 = y_0
+ * The synthesis is linear, so the audio-domain extrapolation equals the usual coefficient-domain one t_k = p_k + momentum (p_k - p_{k-1}).
+ * One wave per (bin, block-clip) analyses, projects and transforms back in registers: neither c nor p reaches memory.
+ *   audio_out = y_{n_iter-1}, the synthesis of a projection; normalize != 0 divides it by its inf-norm exactly as tt_cqt_inverse does
+ *   conv (n_iter, B) or NULL: conv[k][b] = sqrt(sum (|c| - mag)^2 / sum mag^2) over clip b for the input x_k of iteration k -- the
+ *     spectral convergence; exactly 0 when the numerator is 0, +inf when only the denominator is.  fp32 partial sums per wave in a fixed
+ *     lane order, float64 across bins and blocks in a fixed order, no atomics: bit-identical from run to run, as is the audio.
+ * momentum in [0, 1), n_iter >= 1, else TT_E_BADARG.  Scratch: tt_cqt_griffin_lim_scratch_bytes(B * n_blocks, F, sum_len) -- the carve
+ * of tt_cqt_scratch_bytes, two audio buffers and the partial sums. */
+int64_t tt_cqt_griffin_lim_scratch_bytes(int n_clips, int n_bins, int sum_len);
+int tt_cqt_griffin_lim(const tt_cqt_plan* plan, const float* mag, const float* audio_init, float* audio_out, float* conv,
+                       void* scratch, int B, int n_blocks, int n_iter, float momentum, int normalize, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Convolution stack. Replaces torch.nn.Conv2d / ConvTranspose2d / ELU as used by
  * timbre_trap/framework/modules.py (ResidualConv2dBlock :721-777, EncoderBlock :597-655,

@@ -18,6 +18,9 @@
 // kernels through the conj trick, k_absmax / k_scale for the wrapper's inf-norm).
 // The adjoints (tt_cqt_forward_bwd, tt_cqt_inverse_bwd, tt_cqt_forward_mag_bwd, at the end of the file) are the same launches with
 // the two window tables exchanged; only k_band_mag_bwd, the magnitude gradient's band stage, is a kernel of its own.
+// Phase retrieval for the magnitude variants (tt_cqt_griffin_lim, at the end of the file) iterates the analysis launches, k_band_project
+// (analysis band stage, projection onto the target magnitudes and synthesis band stage in one wave) and the synthesis tail, with the
+// momentum applied to the audio (k_gl_extrapolate) and the spectral convergence summed in a fixed order (k_gl_convergence).
 //
 // HBM traffic per block-clip (algorithmic): 264,600 B audio + 4,423,680 B coefficients.  The
 // spectra (2 x 264,600 B) stay in L2 / Infinity Cache between the three launches.
@@ -572,6 +575,109 @@ __global__ __launch_bounds__(256) void k_band_mag_bwd(const float2* __restrict__
     }
 }
 
+// One Griffin-Lim step's band stage (tt_cqt_griffin_lim), one wave per (bin, block-clip), in the mould of k_band_mag_bwd: the coefficients
+// are recomputed in registers exactly as the forward computes them, projected onto the target magnitudes, p = mag c / |c| (mag + 0i
+// where |c| == 0: a silent input gives the zero-phase synthesis, and no 0 / 0), sent through the forward 1024-point FFT in the same wave
+// and LDS slice, and leave as k_band_inv's output on the DUAL windows: neither c nor p reaches memory.  part != nullptr: the wave also
+// writes sum (|c| - mag)^2 and sum mag^2 over its 1024 frames to part[q][bin][0..1] -- fp32, each lane over its 16 frames in order, then
+// a butterfly over the lanes: a fixed order, the same for both sums.
+__global__ __launch_bounds__(256) void k_band_project(const float2* __restrict__ X, const float* __restrict__ mag, float2* __restrict__ S,
+                                                      float* __restrict__ part, const int4* __restrict__ bin_tab,
+                                                      const float* __restrict__ window, const float* __restrict__ dual,
+                                                      const float2* __restrict__ tw1024, int F, int n_blocks, int sum_len) {
+    __shared__ __attribute__((aligned(16))) float2 lds_all[4 * FFT_LDS_F2];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const long q = blockIdx.y;
+    const int bin = blockIdx.x * 4 + wave;
+    if (bin >= F) return;                            // wave-uniform; no workgroup barrier below
+    float2* lds = lds_all + wave * FFT_LDS_F2;
+    const int4 bt = bin_tab[bin];                    // {spec_start, pad, length, win_off}
+    const float2* x = X + q * XPAD + bt.x;
+    const float* w = window + bt.w;
+    const long b = q / n_blocks, blk = q - b * n_blocks;
+    const long Tt = (long)n_blocks * M;
+    const float* tm = mag + (b * F + bin) * Tt + blk * M;
+    float2 v[16];
+    float gm[16];
+#pragma unroll
+    for (int a = 0; a < 16; ++a) {
+        const int m = 64 * a + lane - bt.y;          // index inside the window
+        float2 val = make_float2(0.f, 0.f);
+        if (m >= 0 && m < bt.z) {
+            const float2 xv = x[m];
+            const float g = w[m];
+            val = make_float2(xv.x * g, xv.y * g);
+        }
+        v[a] = val;
+        gm[a] = tm[64 * a + lane];                   // the target magnitude of frame 64 a + lane, in flight under the transform
+    }
+    fft1024_wave<true>(v, lds, tw1024, lane);        // frame 64 r + lane in v[r]
+    const float inv = 1.0f / (float)M;
+    float num = 0.f, den = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const float re = v[r].x * inv, im = v[r].y * inv;
+        const float n = sqrtf(re * re + im * im);    // |c| as the forward epilogue computes it
+        const float t = gm[r] / n;
+        v[r] = (n == 0.f) ? make_float2(gm[r], 0.f) : make_float2(re * t, im * t);
+        const float d = n - gm[r];
+        num = fmaf(d, d, num);
+        den = fmaf(gm[r], gm[r], den);
+        // the sums are complete here: left to itself the compiler sinks both chains below the loop, next to their only use, and keeps
+        // all sixteen |c| and magnitudes alive beside v[] (150 VGPRs, three waves per SIMD; 128 and four with this)
+        asm volatile("" : "+v"(num), "+v"(den));
+    }
+    if (part) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            num += __shfl_xor(num, off, 64);
+            den += __shfl_xor(den, off, 64);
+        }
+        if (lane == 0) reinterpret_cast<float2*>(part)[q * F + bin] = make_float2(num, den);
+    }
+    fft1024_wave<false>(v, lds, tw1024, lane);       // window sample 64 r + lane in v[r]
+    float2* s = S + q * sum_len + bt.w;
+    const float* dl = dual + bt.w;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int m = 64 * r + lane - bt.y;
+        if (m >= 0 && m < bt.z) {
+            const float g = dl[m];
+            s[m] = make_float2(v[r].x * g, v[r].y * g);
+        }
+    }
+}
+
+// conv[b] = sqrt(sum (|c| - mag)^2 / sum mag^2) over the n = n_blocks F partial pairs of clip b (contiguous: q = b n_blocks + blk):
+// float64, thread t over the pairs t, t + 256, .. in order, then a tree over the threads -- a fixed order.  One workgroup per clip.
+__global__ __launch_bounds__(256) void k_gl_convergence(const float2* __restrict__ part, float* __restrict__ conv, int n) {
+    __shared__ double sn[256], sd[256];
+    const int tid = threadIdx.x;
+    const float2* p = part + (long)blockIdx.x * n;
+    double num = 0.0, den = 0.0;
+    for (int i = tid; i < n; i += 256) {
+        const float2 v = p[i];
+        num += (double)v.x;
+        den += (double)v.y;
+    }
+    sn[tid] = num; sd[tid] = den;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off) { sn[tid] += sn[tid + off]; sd[tid] += sd[tid + off]; }
+        __syncthreads();
+    }
+    if (tid == 0) conv[blockIdx.x] = (sn[0] == 0.0) ? 0.f : (float)sqrt(sn[0] / sd[0]);     // den == 0 alone: +inf
+}
+
+// the momentum of fast Griffin-Lim in the audio domain: x = y + alpha (y - y_prev).  x may be y_prev's storage (each thread reads its pair
+// before it writes it), so neither carries __restrict__.
+__global__ __launch_bounds__(256) void k_gl_extrapolate(const float2* __restrict__ y, const float2* y_prev, float2* x, float alpha, long n2) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n2; i += (long)gridDim.x * 256) {
+        const float2 c = y[i], p = y_prev[i];
+        x[i] = make_float2(fmaf(alpha, c.x - p.x, c.x), fmaf(alpha, c.y - p.y, c.y));
+    }
+}
+
 // Overlap-add of the windowed bands in the spectrum (deterministic gather through a CSR built on the
 // host), then the real-IFFT pre-split:  Zc[k] = conj(E[k] + i O[k]).
 __global__ __launch_bounds__(256) void k_spec_gather(const float2* __restrict__ S, float2* __restrict__ Zc,
@@ -799,4 +905,82 @@ extern "C" int tt_cqt_forward_mag_bwd(const tt_cqt_plan* plan, const float* audi
                        reinterpret_cast<const float2*>(plan->tw1024), F, n_blocks, plan->sum_len);
     TT_LAUNCH_CHECK();
     return cqt_synth_tail<true>(plan, s, daudio, Q, 0, st);
+}
+
+// ---- phase retrieval (version 20) ----------------------------------------------------------------------------------------------------
+// Griffin-Lim on the transform's own launches: per iteration cqt_spectrum(x_k), k_band_project (analysis, projection onto the target
+// magnitudes and the band stage of the synthesis in one wave), the synthesis tail into y_k, and x_{k+1} = y_k + alpha (y_k - y_{k-1}) in
+// the audio domain -- the synthesis is linear, so this is the coefficient-domain momentum of fast Griffin-Lim without a second
+// coefficient buffer.  Two audio buffers, exchanged by pointer: y_k lands in the one that does not hold y_{k-1} (x_k is dead once its
+// spectrum is taken), and x_{k+1} overwrites y_{k-1} in place.
+
+namespace {
+struct GlScratch {
+    float* a;        // [Q][2 NC]
+    float* b;
+    float* part;     // [Q][F][2]
+};
+inline GlScratch gl_carve(void* base, int Q, int F, int sum_len) {
+    char* p = reinterpret_cast<char*>(base) + tt_cqt_scratch_bytes(Q, F, sum_len);
+    GlScratch g;
+    g.a = reinterpret_cast<float*>(p);                p += align256((int64_t)Q * NC * 8);
+    g.b = reinterpret_cast<float*>(p);                p += align256((int64_t)Q * NC * 8);
+    g.part = reinterpret_cast<float*>(p);
+    return g;
+}
+}  // namespace
+
+extern "C" int64_t tt_cqt_griffin_lim_scratch_bytes(int n_clips, int n_bins, int sum_len) {
+    if (n_clips <= 0 || n_bins <= 0 || sum_len <= 0) return 0;
+    return tt_cqt_scratch_bytes(n_clips, n_bins, sum_len) + 2 * align256((int64_t)n_clips * NC * 8) +
+           align256((int64_t)n_clips * n_bins * 8);
+}
+
+extern "C" int tt_cqt_griffin_lim(const tt_cqt_plan* plan, const float* mag, const float* audio_init, float* audio_out, float* conv,
+                                  void* scratch, int B, int n_blocks, int n_iter, float momentum, int normalize, void* stream) {
+    if (!plan || !mag || !audio_out || !scratch || B <= 0 || n_blocks <= 0 || n_iter < 1 || !(momentum >= 0.f && momentum < 1.f))
+        return TT_E_BADARG;
+    int rc = cqt_set_attrs();
+    if (rc) return rc;
+    hipStream_t st = tt_stream(stream);
+    const int Q = B * n_blocks, F = plan->n_bins;
+    Scratch s = carve(scratch, Q, plan->sum_len);
+    GlScratch g = gl_carve(scratch, Q, F, plan->sum_len);
+    const long n2 = (long)Q * NC;                    // float2 per audio buffer
+    const float* x = audio_init;
+    if (!x) {
+        TT_HIP(hipMemsetAsync(g.a, 0, (size_t)n2 * 8, st));
+        x = g.a;
+    }
+    float* y_prev = nullptr;
+    for (int k = 0; k < n_iter; ++k) {
+        const bool last = k == n_iter - 1;
+        float* y = last ? audio_out : (y_prev == g.b ? g.a : g.b);
+        rc = cqt_spectrum(plan, x, s, Q, st);
+        if (rc) return rc;
+        // X is read here for the last time: the tail reuses its storage as Zc
+        hipLaunchKernelGGL(k_band_project, dim3((F + 3) / 4, Q), dim3(256), 0, st, s.X, mag, s.S, conv ? g.part : (float*)nullptr,
+                           reinterpret_cast<const int4*>(plan->bin_tab), plan->window, plan->dual,
+                           reinterpret_cast<const float2*>(plan->tw1024), F, n_blocks, plan->sum_len);
+        TT_LAUNCH_CHECK();
+        if (conv) {
+            hipLaunchKernelGGL(k_gl_convergence, dim3(B), dim3(256), 0, st, reinterpret_cast<const float2*>(g.part),
+                               conv + (long)k * B, n_blocks * F);
+            TT_LAUNCH_CHECK();
+        }
+        rc = cqt_synth_tail<false>(plan, s, y, Q, last ? normalize : 0, st);
+        if (rc) return rc;
+        if (last) break;
+        if (y_prev && momentum != 0.f) {
+            // x_{k+1} over y_{k-1}; momentum == 0 is the plain iteration: x_{k+1} is y_k itself
+            hipLaunchKernelGGL(k_gl_extrapolate, dim3(2048), dim3(256), 0, st, reinterpret_cast<const float2*>(y),
+                               reinterpret_cast<const float2*>(y_prev), reinterpret_cast<float2*>(y_prev), momentum, n2);
+            TT_LAUNCH_CHECK();
+            x = y_prev;
+        } else {
+            x = y;
+        }
+        y_prev = y;
+    }
+    return 0;
 }

@@ -79,6 +79,8 @@ _PROTOS = {
     'tt_cqt_forward_mag_bwd': (c_int, [ctypes.POINTER(CqtPlan), P, P, P, P, I, I, P]),
     'tt_cqt_generic_forward_bwd': (c_int, [ctypes.POINTER(CqtGenericPlan), P, P, P, I, I, I, P]),
     'tt_cqt_generic_inverse_bwd': (c_int, [ctypes.POINTER(CqtGenericPlan), P, P, P, I, I, I, P]),
+    'tt_cqt_griffin_lim_scratch_bytes': (c_int64, [I, I, I]),
+    'tt_cqt_griffin_lim': (c_int, [ctypes.POINTER(CqtPlan), P, P, P, P, P, I, I, I, F_, I, P]),
     'tt_conv2d': (c_int, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, L, L, L, L, I, P]),
     'tt_conv2d_wgrad': (c_int, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, L, L, L, L, P]),
     'tt_elu_bwd': (c_int, [P, P, P, L, P]),

@@ -9,6 +9,9 @@ the gfx950 kernels of csrc/cqt.hip through the C ABI ``tt_cqt_forward`` / ``tt_c
 ``tt_cqt_inverse_bwd`` / ``tt_cqt_forward_mag_bwd``; derivation in DESIGN.md 6j).  ``forward`` and ``decode`` stay detached: the
 reference wraps exactly those two in ``torch.no_grad()`` (cqtwrapper.py:65, :199).
 
+``griffin_lim`` and ``from_decibels`` are additions: the way from the magnitude variants' output back to audio (``tt_cqt_griffin_lim``,
+DESIGN.md 6k), which the reference lacks.
+
 The frame/time helpers (reference :215-308) stay pure Python/NumPy: the datasets call them from
 DataLoader worker processes, so they must not touch the HIP runtime, and the object stays
 fork- and pickle-safe (no library handle is stored on it).
@@ -339,6 +342,99 @@ class CQT(nn.Module):
             _hip.check(inverse(ctypes.byref(ps), _hip.ptr(c), _hip.ptr(audio), _hip.ptr(scratch),
                                B, n_blocks, int(is_complex), int(bool(normalize)), _hip.stream_ptr()), 'tt_cqt_inverse')
         return audio
+
+    # ---- phase retrieval: audio from magnitudes (no reference counterpart; the magnitude variants' way to sonify.py) ----------------
+
+    # True: the composed route (analysis with complex output, the projection as torch expressions, synthesis) also on the specialised
+    # plan, where griffin_lim otherwise makes the one C call -- the yardstick of tests and of tools/kb_griffin_lim.py
+    _gl_composed = False
+
+    def griffin_lim(self, magnitude, n_iter=32, momentum=0.99, audio_init=None, normalize=True, return_convergence=False):
+        """
+        Audio whose transform has the given magnitudes, by the Griffin-Lim iteration with the momentum of "fast Griffin-Lim":
+
+            c = analysis(x_k);  p = magnitude c / |c|  (magnitude + 0i where |c| == 0);  y_k = synthesis(p);
+            x_{k+1} = y_k + momentum (y_k - y_{k-1}),  x_1 = y_0
+
+        magnitude : fp32 Tensor (B x F x T) or (B x 1 x F x T) on the device, taken as given (no clamp)
+        audio_init : Tensor (B x 1 x N) the start x_0, e.g. the mixture the magnitudes were estimated from; None = silence, which makes
+          y_0 the zero-phase synthesis
+        returns audio (B x 1 x N) = y_{n_iter-1}, divided by its infinity norm as ``decode`` does if ``normalize``; with
+        ``return_convergence`` also the (n_iter x B) tensor of sqrt(sum (|c| - magnitude)^2 / sum magnitude^2) per clip, row k measured
+        on the input x_k of iteration k.
+
+        Always detached.  The reference configuration runs tt_cqt_griffin_lim: all iterations enqueued by one call, the coefficients
+        never in memory.  Other block lengths (correct, untuned, as everywhere on the any-length path) loop here over the any-length
+        analysis and synthesis with the projection, the convergence and the extrapolation as torch expressions.
+        """
+        _hip.require_cuda(magnitude, audio_init)
+        if magnitude.dim() == 4 and magnitude.size(1) == 1:
+            magnitude = magnitude[:, 0]
+        if magnitude.dim() != 3 or magnitude.size(1) != self.n_bins:
+            raise ValueError('magnitudes of shape %s, expected (B, %d, T) or (B, 1, %d, T)' % (tuple(magnitude.shape), self.n_bins, self.n_bins))
+        B, T = magnitude.size(0), magnitude.size(2)
+        if B == 0 or T == 0 or T % self.max_window_length:
+            raise ValueError('frame count %d is not a positive multiple of %d' % (T, self.max_window_length))
+        if int(n_iter) != n_iter or n_iter < 1:
+            raise ValueError('n_iter = %r: at least one iteration' % (n_iter,))
+        alpha = ctypes.c_float(momentum).value                      # the value the kernels see
+        if not 0.0 <= alpha < 1.0:
+            raise ValueError('momentum = %r is outside [0, 1)' % (momentum,))
+        n_iter, n_blocks = int(n_iter), T // self.max_window_length
+        with torch.no_grad():
+            mag = magnitude.detach().to(torch.float32).contiguous()
+            x = None
+            if audio_init is not None:
+                if audio_init.numel() != B * n_blocks * self.block_length or audio_init.size(0) != B:
+                    raise ValueError('audio_init of shape %s for %d clips of %d blocks of %d samples'
+                                     % (tuple(audio_init.shape), B, n_blocks, self.block_length))
+                x = audio_init.detach().reshape(B, -1).to(torch.float32).contiguous()
+            if not self._fast or self._gl_composed:
+                return self._griffin_lim_composed(mag, x, n_iter, alpha, normalize, return_convergence)
+            lib = _hip.lib()
+            ps = self._plan_struct(mag.device)
+            nbytes = lib.tt_cqt_griffin_lim_scratch_bytes(B * n_blocks, self.n_bins, self._sum_len)
+            if nbytes <= 0:
+                raise RuntimeError('the constant-Q transform plan was rejected by the library')
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=mag.device)
+            audio = torch.empty((B, 1, n_blocks * self.block_length), dtype=torch.float32, device=mag.device)
+            conv = torch.empty((n_iter, B), dtype=torch.float32, device=mag.device) if return_convergence else None
+            with _hip.timed('cqt_griffin_lim'):
+                _hip.check(lib.tt_cqt_griffin_lim(ctypes.byref(ps), _hip.ptr(mag), _hip.ptr(x), _hip.ptr(audio), _hip.ptr(conv),
+                                                  _hip.ptr(scratch), B, n_blocks, n_iter, alpha, int(bool(normalize)), _hip.stream_ptr()),
+                           'tt_cqt_griffin_lim')
+            return (audio, conv) if return_convergence else audio
+
+    def _griffin_lim_composed(self, mag, x, n_iter, alpha, normalize, return_convergence):
+        """The same iteration on the two transforms' own entry points (on either plan): the coefficients and their projection pass
+        through memory."""
+        B = mag.size(0)
+        m = mag[:, None]
+        if x is None:
+            x = torch.zeros((B, m.size(-1) // self.max_window_length * self.block_length), dtype=torch.float32, device=mag.device)
+        conv, y_prev = [], None
+        for k in range(n_iter):
+            c = self._analysis(x, True)
+            n = c.abs()
+            if return_convergence:
+                num, den = ((n - m).double() ** 2).sum((1, 2, 3)), (m.double() ** 2).sum((1, 2, 3))
+                conv.append(torch.where(num == 0, torch.zeros_like(num), (num / den).sqrt()).float())
+            p = torch.where(n == 0, torch.complex(m, torch.zeros_like(m)), c * (m / n))
+            last = k == n_iter - 1
+            audio = self._synthesis(p, normalize and last)
+            if last:
+                break
+            y = audio.reshape(B, -1)
+            x = y if y_prev is None or alpha == 0.0 else torch.add(y, y - y_prev, alpha=alpha)
+            y_prev = y
+        return (audio, torch.stack(conv)) if return_convergence else audio
+
+    @staticmethod
+    def from_decibels(decibels):
+        """The inverse of ``to_decibels(rescale=True)`` up to each item's peak: 10^(4 (d - 1)), i.e. 1 at the item's maximum and 1e-4 on
+        the 80 dB floor.  The scale that ``to_decibels`` removed is lost; the infinity norm of ``decode`` / ``griffin_lim`` removes it
+        anyway."""
+        return torch.pow(10.0, 4.0 * (decibels - 1.0))
 
     # ---- layout helpers (reference cqtwrapper.py:74-182), stock tensor views ----------------------
 

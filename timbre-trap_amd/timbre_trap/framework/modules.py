@@ -386,6 +386,11 @@ class TimbreTrap(nn.Module):
         """audio (B,1,N) -> re-synthesised audio (B,1,L)."""
         return self.sliCQ.decode(self.chunked_inference(audio_in, False))
 
+    def sonify(self, coefficients):
+        """coefficients (B,2,F,T) or complex (B,1,F,T) -> audio (B,1,N): what experiments/sonify.py:109 does with the model's output.
+        The magnitude variants override it, so that loop runs on any variant with this one call."""
+        return self.sliCQ.decode(coefficients)
+
     def forward(self, audio, consistency=False):
         """
         One pass for training / evaluation (reference modules.py:338-393): returns
@@ -480,6 +485,11 @@ class TimbreTrapMag(TimbreTrap):
         """logits (B,1,F,T) -> activations (B,F,T): tanh (reference modules.py:980-997)."""
         return ops.Activations1Fn.apply(coefficients.squeeze(-3))
 
+    def sonify(self, coefficients, audio_init=None, n_iter=32, momentum=0.99):
+        """magnitudes (B,1,F,T) as the model returns them -> audio (B,1,N) by phase retrieval (CQT.griffin_lim), inf-normalised as
+        ``decode`` normalises.  ``audio_init``: the start of the iteration; the input mixture is the usual "mixture phase" choice."""
+        return self.sliCQ.griffin_lim(coefficients, n_iter=n_iter, momentum=momentum, audio_init=audio_init)
+
 
 class TimbreTrapMagDB(TimbreTrapMag):
     """
@@ -496,6 +506,10 @@ class TimbreTrapMagDB(TimbreTrapMag):
     def to_activations(self, coefficients):
         """logits (B,1,F,T) -> activations (B,F,T): a view (reference modules.py:1058-1075)."""
         return coefficients.squeeze(-3)
+
+    def sonify(self, coefficients, audio_init=None, n_iter=32, momentum=0.99):
+        """rescaled decibels (B,1,F,T) as the model returns them -> audio (B,1,N): CQT.from_decibels, then TimbreTrapMag.sonify."""
+        return TimbreTrapMag.sonify(self, self.sliCQ.from_decibels(coefficients), audio_init, n_iter, momentum)
 
 
 class FiLM(nn.Module):
