@@ -70,6 +70,13 @@ int         tt_set_cu_limit(int cus);
  *   window  [sumL]  float   ragged analysis windows   (forward)
  *   dual    [sumL]  float   ragged synthesis windows  (inverse)
  *   gat_off [33077] int32 , gat_idx [sumL] int32   CSR: spectral index -> ragged positions
+ *
+ * Alignment (every tt_cqt_* entry point, the any-length and Griffin-Lim ones included; tests/test_gpu_cqt_abi_parity.py holds it):
+ * `scratch` is 256-byte aligned and every table of a plan 16-byte aligned.  Entry points of csrc/cqt.hip: audio in either direction
+ * (audio, daudio, audio_init, audio_out) 8 bytes -- it moves as pairs of samples; coefficients WRITTEN (out of tt_cqt_forward /
+ * tt_cqt_forward_mag, dcoeffs of tt_cqt_inverse_bwd) 16 bytes; coefficients READ (coeffs, dcoeffs of tt_cqt_forward_bwd) 4 bytes as
+ * planes, 8 as interleaved complex; dmag, mag and conv 4 bytes.  Entry points of csrc/cqt_generic.hip: 4 bytes everywhere, 8 for
+ * interleaved complex coefficients.  A scratch or data pointer that breaks its rule is refused with TT_E_BADARG before the first launch.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
     const float*   tw675;
@@ -86,7 +93,8 @@ typedef struct {
     int32_t        sum_len;    /* sum of window lengths */
 } tt_cqt_plan;
 
-/* bytes of scratch the two calls below need for `n_clips` = B * n_blocks block-clips */
+/* bytes of scratch the two calls below need for `n_clips` = B * n_blocks block-clips; 0 for n_clips, n_bins or sum_len <= 0, as
+ * tt_cqt_griffin_lim_scratch_bytes.  tt_cqt_generic_scratch_bytes: 0 for n_clips <= 0, -1 for a plan the entry points refuse. */
 int64_t tt_cqt_scratch_bytes(int n_clips, int n_bins, int sum_len);
 
 /* audio (B, 1, n_blocks*66150) -> out (B, 2, F, n_blocks*1024), ch0 = re, ch1 = im.

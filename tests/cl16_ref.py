@@ -100,11 +100,11 @@ class Arena:
         self.win = {}
         self.pos = GUARD
 
-    def _add(self, name, kind, dtype, shape, vals, shift):
+    def _add(self, name, kind, dtype, shape, vals, shift, align=16):
         item = torch.empty((), dtype=dtype).element_size()
-        assert shift % item == 0
+        assert shift % item == 0 and align % 16 == 0
         nbytes = int(math.prod(shape)) * item
-        start = (self.pos + 15) // 16 * 16 + shift
+        start = (self.pos + align - 1) // align * align + shift
         if vals is not None:
             assert vals.dtype == dtype and tuple(vals.shape) == tuple(shape)
             vals = vals.contiguous().reshape(-1).view(torch.uint8).clone()
@@ -120,8 +120,9 @@ class Arena:
     def acc(self, name, vals, shift=0):
         self._add(name, 'acc', vals.dtype, vals.shape, vals, shift)
 
-    def scratch(self, name, nbytes, shift=0):
-        self._add(name, 'scratch', torch.uint8, (int(nbytes),), None, shift)
+    def scratch(self, name, nbytes, shift=0, align=16):
+        """``align``: the boundary (a multiple of 16 bytes, counted from the start of the buffer) the window starts on before ``shift``"""
+        self._add(name, 'scratch', torch.uint8, (int(nbytes),), None, shift, align)
 
     def build(self):
         total = (self.pos + 15) // 16 * 16

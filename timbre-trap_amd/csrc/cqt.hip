@@ -729,10 +729,15 @@ inline Scratch carve(void* base, int Q, int sum_len) {
 
 constexpr int LDS_ROWS = (N1 + ROWS * 25 * YS_PITCH) * 8;   // 44,600 B
 
+// The alignment contract of include/ttrap.h, checked before the first launch: the carve above is in 256-byte steps from `scratch`; audio
+// is read and written as float2 pairs; k_band_fwd writes the coefficient planes 16 bytes per lane; k_band_inv reads planes one float at
+// a time and interleaved complex values as float2; dmag, mag and conv move one float at a time.  NULL counts as aligned.
+inline bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+
 }  // namespace
 
 extern "C" int64_t tt_cqt_scratch_bytes(int n_clips, int n_bins, int sum_len) {
-    (void)n_bins;
+    if (n_clips <= 0 || n_bins <= 0 || sum_len <= 0) return 0;
     return 256 + align256((int64_t)n_clips * NC * 8) + align256((int64_t)n_clips * XPAD * 8) +
            align256((int64_t)n_clips * sum_len * 8);
 }
@@ -785,6 +790,7 @@ static int cqt_bands_fwd(const tt_cqt_plan* plan, const float* window, const Scr
 static int cqt_forward(const tt_cqt_plan* plan, const float* audio, float* out, void* scratch, int B, int n_blocks, int out_complex,
                        bool mag, void* stream) {
     if (!plan || !audio || !out || !scratch || B <= 0 || n_blocks <= 0) return TT_E_BADARG;
+    if (!aligned_to(scratch, 256) || !aligned_to(audio, 8) || !aligned_to(out, 16)) return TT_E_BADARG;
     int rc = cqt_set_attrs();
     if (rc) return rc;
     hipStream_t st = tt_stream(stream);
@@ -840,6 +846,7 @@ template <bool ADJ>
 static int cqt_inverse(const tt_cqt_plan* plan, const float* dual, const float* coeffs, float* audio, void* scratch, int B, int n_blocks,
                        int in_complex, int normalize, void* stream) {
     if (!plan || !coeffs || !audio || !scratch || B <= 0 || n_blocks <= 0) return TT_E_BADARG;
+    if (!aligned_to(scratch, 256) || !aligned_to(audio, 8) || !aligned_to(coeffs, in_complex ? 8 : 4)) return TT_E_BADARG;
     int rc = cqt_set_attrs();
     if (rc) return rc;
     hipStream_t st = tt_stream(stream);
@@ -879,6 +886,7 @@ extern "C" int tt_cqt_forward_bwd(const tt_cqt_plan* plan, const float* dcoeffs,
 extern "C" int tt_cqt_inverse_bwd(const tt_cqt_plan* plan, const float* daudio, float* dcoeffs, void* scratch, int B, int n_blocks,
                                   int out_complex, void* stream) {
     if (!plan || !daudio || !dcoeffs || !scratch || B <= 0 || n_blocks <= 0) return TT_E_BADARG;
+    if (!aligned_to(scratch, 256) || !aligned_to(daudio, 8) || !aligned_to(dcoeffs, 16)) return TT_E_BADARG;
     int rc = cqt_set_attrs();
     if (rc) return rc;
     hipStream_t st = tt_stream(stream);
@@ -892,6 +900,7 @@ extern "C" int tt_cqt_inverse_bwd(const tt_cqt_plan* plan, const float* daudio, 
 extern "C" int tt_cqt_forward_mag_bwd(const tt_cqt_plan* plan, const float* audio, const float* dmag, float* daudio, void* scratch, int B,
                                       int n_blocks, void* stream) {
     if (!plan || !audio || !dmag || !daudio || !scratch || B <= 0 || n_blocks <= 0) return TT_E_BADARG;
+    if (!aligned_to(scratch, 256) || !aligned_to(audio, 8) || !aligned_to(daudio, 8) || !aligned_to(dmag, 4)) return TT_E_BADARG;
     int rc = cqt_set_attrs();
     if (rc) return rc;
     hipStream_t st = tt_stream(stream);
@@ -939,6 +948,8 @@ extern "C" int64_t tt_cqt_griffin_lim_scratch_bytes(int n_clips, int n_bins, int
 extern "C" int tt_cqt_griffin_lim(const tt_cqt_plan* plan, const float* mag, const float* audio_init, float* audio_out, float* conv,
                                   void* scratch, int B, int n_blocks, int n_iter, float momentum, int normalize, void* stream) {
     if (!plan || !mag || !audio_out || !scratch || B <= 0 || n_blocks <= 0 || n_iter < 1 || !(momentum >= 0.f && momentum < 1.f))
+        return TT_E_BADARG;
+    if (!aligned_to(scratch, 256) || !aligned_to(audio_init, 8) || !aligned_to(audio_out, 8) || !aligned_to(mag, 4) || !aligned_to(conv, 4))
         return TT_E_BADARG;
     int rc = cqt_set_attrs();
     if (rc) return rc;

@@ -266,6 +266,10 @@ struct GScratch {
     unsigned* peak;
 };
 
+// The alignment contract of include/ttrap.h, checked before the first launch: the carve below is in 256-byte steps from `scratch`; audio and
+// coefficient planes move one float at a time, interleaved complex coefficients as float2.  NULL counts as aligned.
+inline bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+
 inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
 inline bool plan_ok(const tt_cqt_gplan* p) {
@@ -293,7 +297,8 @@ inline GScratch gcarve(void* scratch, const tt_cqt_gplan* p, int64_t Q) {
 }  // namespace
 
 extern "C" int64_t tt_cqt_generic_scratch_bytes(const tt_cqt_gplan* plan, int n_clips) {
-    if (!plan_ok(plan) || n_clips <= 0) return -1;
+    if (!plan_ok(plan)) return -1;
+    if (n_clips <= 0) return 0;
     return 256 + 2 * align256(work_elems(plan, n_clips) * 8) + align256((int64_t)n_clips * (plan->N / 2 + 1) * 8);
 }
 
@@ -302,6 +307,7 @@ template <bool ADJ>
 static int g_forward(const tt_cqt_gplan* plan, const float* window, const float* audio, float* out, void* scratch, int B, int n_blocks,
                      int out_complex, void* stream) {
     if (!plan_ok(plan) || !audio || !out || !scratch || B <= 0 || n_blocks <= 0) return TT_E_BADARG;
+    if (!aligned_to(scratch, 256) || !aligned_to(audio, 4) || !aligned_to(out, out_complex ? 8 : 4)) return TT_E_BADARG;
     hipStream_t st = tt_stream(stream);
     const long Q = (long)B * n_blocks;
     const int N = plan->N, NH1 = N / 2 + 1, F = plan->n_bins, logP = ilog2(plan->P), logM = ilog2(plan->M);
@@ -340,6 +346,7 @@ template <bool ADJ>
 static int g_inverse(const tt_cqt_gplan* plan, const float* dual, const float* coeffs, float* audio, void* scratch, int B, int n_blocks,
                      int in_complex, int normalize, void* stream) {
     if (!plan_ok(plan) || !coeffs || !audio || !scratch || B <= 0 || n_blocks <= 0) return TT_E_BADARG;
+    if (!aligned_to(scratch, 256) || !aligned_to(audio, 4) || !aligned_to(coeffs, in_complex ? 8 : 4)) return TT_E_BADARG;
     hipStream_t st = tt_stream(stream);
     const long Q = (long)B * n_blocks;
     const int N = plan->N, NH1 = N / 2 + 1, F = plan->n_bins, logP = ilog2(plan->P), logM = ilog2(plan->M);

@@ -35,6 +35,12 @@ _GENERIC_TABLES = ('chirp', 'bfilt', 'twP', 'twM', 'bin_tab', 'window', 'dual', 
 FORCE_GENERIC = False
 
 
+def _aligned(t, nbytes):
+    """``t`` (contiguous) at an address the kernels accept (include/ttrap.h: audio moves as pairs of samples, 8 bytes; interleaved complex
+    coefficients 8): a contiguous view into a larger tensor may start anywhere, a copy starts on an allocation."""
+    return t if t.data_ptr() % nbytes == 0 else t.clone()
+
+
 def _wants_grad(t):
     return torch.is_grad_enabled() and t.requires_grad
 
@@ -195,13 +201,13 @@ class CQT(nn.Module):
             raise ValueError('audio length %d is not a multiple of the block length %d (use pad_to_block_length)'
                              % (audio.size(-1), self.block_length))
         lead = audio.shape[:-1]
-        a = audio.reshape(-1, audio.size(-1)).to(torch.float32).contiguous()
+        a = _aligned(audio.reshape(-1, audio.size(-1)).to(torch.float32).contiguous(), 8)
         return a, lead
 
     def _analysis(self, a, complex_out, adjoint=False):
         """a (B, n_blocks N) contiguous fp32 -> (B, 2, F, T) planes or complex (B, 1, F, T).  ``adjoint``: the gradient of the synthesis
         w.r.t. its coefficients instead (tt_cqt_inverse_bwd: the same pipeline on the dual windows, times 2M / N)."""
-        a = a.contiguous()
+        a = _aligned(a.contiguous(), 8)
         B, n_blocks = a.size(0), a.size(1) // self.block_length
         T = n_blocks * self.max_window_length
         lib = _hip.lib()
@@ -317,7 +323,7 @@ class CQT(nn.Module):
         _hip.require_cuda(coefficients)
         is_complex = coefficients.is_complex()
         if is_complex:
-            c = torch.view_as_real(coefficients.to(torch.complex64).contiguous())
+            c = torch.view_as_real(_aligned(coefficients.to(torch.complex64).contiguous(), 8))
             B = c.size(0)
             T = c.size(-2)
         else:
@@ -388,7 +394,7 @@ class CQT(nn.Module):
                 if audio_init.numel() != B * n_blocks * self.block_length or audio_init.size(0) != B:
                     raise ValueError('audio_init of shape %s for %d clips of %d blocks of %d samples'
                                      % (tuple(audio_init.shape), B, n_blocks, self.block_length))
-                x = audio_init.detach().reshape(B, -1).to(torch.float32).contiguous()
+                x = _aligned(audio_init.detach().reshape(B, -1).to(torch.float32).contiguous(), 8)
             if not self._fast or self._gl_composed:
                 return self._griffin_lim_composed(mag, x, n_iter, alpha, normalize, return_convergence)
             lib = _hip.lib()
