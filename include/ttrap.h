@@ -731,6 +731,34 @@ int tt_note_spans(const double* times, int N, const double* intervals, int L, in
 int tt_note_count(const int* lo, const int* hi, int L, int N, int* count, void* stream);
 int tt_note_fill(const int* lo, const int* hi, int L, int N, const int64_t* off, int64_t capacity, int* note_idx, void* stream);
 
+/* ---- note events from activation maps (csrc/events.hip; version 21) ------------------------------------------------------------------
+ * The way back from the block above: a (B, F, T) activation map (TimbreTrap.transcribe's output; fp32, T contiguous) to note events --
+ * pitch row, onset frame, end frame, strength -- where the map is.  No reference counterpart: the reference stops at per-frame lists.
+ * A bin is active under tt_peak_pick's predicate of `mode` 1 or 2 (threshold, f_valid: as for tt_mpe_count; a NaN never passes).  Bins are
+ * grouped into P pitch rows by group_off (P + 1 int32 on the device, ascending, within [0, F]): row p owns the bins
+ * [group_off[p], group_off[p + 1]), possibly none; frame t of row p is active (a = 1) when one of its bins is, with value v = the largest
+ * x among the row's active bins.  With G = max_gap every maximal run of at most G zeros of a row that has a one on both sides inside
+ * [0, T) is filled; the candidate notes are the maximal runs [t0, t1] of the filled row (a = 1 at both ends); a candidate is kept iff
+ * t1 - t0 + 1 >= min_frames.  Candidates are numbered in ascending (item, row, onset) order.  Nothing here uses atomics or reads the
+ * environment; every offset is 64-bit; the grids are one-dimensional, so B P ceil(T / 64) may be any size; the results do not depend on
+ * the launch geometry.  0 <= max_gap <= 63, min_frames >= 1, sizes >= 1, no null pointer: else TT_E_BADARG and nothing is launched.
+ *   tt_events_mask    mask[(b P + p) W + w], W = ceil(T / 64): bit i = a[b, p, 64 w + i]; the bits beyond T are zero
+ *   tt_events_count   n_on / n_end[(b P + p) W + w] = candidates that start / end (last frame) in word w of the row, from that word and
+ *                     its two neighbours IN THE SAME ROW.  Per row the two counts have equal totals and the i-th start belongs with the
+ *                     i-th end, so the two exclusive prefix sums over all B P W entries (formed by the caller, int64) index the same slots
+ *   tt_events_fill    item / row / onset of candidate on_off[.] + rank, end (t1 + 1, exclusive) of candidate end_off[.] + rank; nothing is
+ *                     written at or beyond `capacity`
+ *   tt_events_finish  for candidate i < n_notes (the arrays tt_events_fill wrote): n_active[i] = a = 1 frames in [t0, t1]; peak[i] = max of
+ *                     v over them (an exact fp32 value of x; +inf allowed); keep[i] = (t1 - t0 + 1 >= min_frames) */
+int tt_events_mask(const float* x, int B, int F, int T, double threshold, int mode, int f_valid, const int* group_off, int P,
+                   uint64_t* mask, void* stream);
+int tt_events_count(const uint64_t* mask, int B, int P, int T, int max_gap, int* n_on, int* n_end, void* stream);
+int tt_events_fill(const uint64_t* mask, int B, int P, int T, int max_gap, const int64_t* on_off, const int64_t* end_off, int64_t capacity,
+                   int* item, int* row, int* onset, int* end, void* stream);
+int tt_events_finish(const float* x, int B, int F, int T, double threshold, int mode, int f_valid, const int* group_off, int P,
+                     const uint64_t* mask, const int* item, const int* row, const int* onset, const int* end, int64_t n_notes,
+                     int min_frames, int* n_active, float* peak, int* keep, void* stream);
+
 /* ---- frame-level pitch annotations to batched targets (csrc/pitch.hip; version 14) ---------------------------------------------------
  * Replaces, per item of an MPEDataset, PitchDataset.resample_multi_pitch (timbre_trap/datasets/PitchDataset.py:194-231: interp1d over the
  * track's frame times, then a list comprehension over the item's frames) followed by PitchDataset.multi_pitch_to_activations

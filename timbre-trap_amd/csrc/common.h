@@ -91,6 +91,14 @@ __device__ __forceinline__ float act_grad_from_out(float dy, float y, int act) {
     return dy;
 }
 
+// The predicate of tt_peak_pick's modes 1 and 2, shared by every kernel that decides which bins of an activation map are active
+// (losses.hip k_peak_pick, mpe.hip k_mpe_compact, events.hip): v at the bin, up / dn its neighbours along F, all three already read as
+// zero where a row is masked or lies beyond an end.  Compared in double like the reference's ndarray >= t; a NaN never passes.
+__device__ __forceinline__ bool tt_pick_pass(float v, float up, float dn, double thr, int mode) {
+    const bool peak = mode == 1 || (v > up && v > dn);
+    return peak && (double)v >= thr;
+}
+
 // 64-lane wave reductions
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

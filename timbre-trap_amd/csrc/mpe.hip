@@ -56,8 +56,7 @@ __global__ __launch_bounds__(64) void k_mpe_compact(const float* __restrict__ x,
         for (int i = 0; i < MPE_ROWS; ++i) {
             const int f = f0 + i;
             if (f < fv) {
-                const bool peak = mode == 1 || (cur > up && cur > nx[i]);
-                if (peak && (double)cur >= thr) emit(f);
+                if (tt_pick_pass(cur, up, nx[i], thr, mode)) emit(f);
                 up = cur;
                 cur = nx[i];
             }

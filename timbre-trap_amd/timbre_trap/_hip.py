@@ -40,7 +40,9 @@ SOURCES = ['cqt.hip', 'cqt_generic.hip', 'conv_generic.hip', 'conv_mfma.hip', 'c
            'film.hip',
            # random stem mixtures of a training batch: excerpt gather-and-sum of the audio, segmented sum-and-clamp of the target maps
            # (StemMixingDataset.__getitem__)
-           'mix.hip']
+           'mix.hip',
+           # note events (pitch row, onset, end, strength) from activation maps: bit-word run detection with gap filling
+           'events.hip']
 
 _lib = None
 
@@ -201,6 +203,10 @@ _PROTOS = {
     'tt_note_spans': (c_int, [P, I, P, I, P, P, P]),
     'tt_note_count': (c_int, [P, P, I, I, P, P]),
     'tt_note_fill': (c_int, [P, P, I, I, P, L, P, P]),
+    'tt_events_mask': (c_int, [P, I, I, I, ctypes.c_double, I, I, P, I, P, P]),
+    'tt_events_count': (c_int, [P, I, I, I, I, P, P, P]),
+    'tt_events_fill': (c_int, [P, I, I, I, I, P, P, L, P, P, P, P, P]),
+    'tt_events_finish': (c_int, [P, I, I, I, ctypes.c_double, I, I, P, I, P, P, P, P, P, L, I, P, P, P, P]),
     'tt_pitch_tile_frames': (c_int, []),
     'tt_pitch_max_bins': (c_int, []),
     'tt_pitch_max_radius': (c_int, []),

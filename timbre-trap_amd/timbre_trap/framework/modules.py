@@ -382,6 +382,12 @@ class TimbreTrap(nn.Module):
         """audio (B,1,N) -> multi-pitch activations (B,F,T)."""
         return self.to_activations(self.chunked_inference(audio, True))
 
+    def transcribe_notes(self, audio, **kwargs):
+        """audio (B,1,N) -> note events (utils.events.NoteEvents: item, row, onset, end, n_active, peak, pitch) formed on the device from
+        ``transcribe(audio)``; ``kwargs`` as for ``utils.note_events`` (t, peaks_only, n_valid_bins, resolution, max_gap, min_frames, order)."""
+        from ..utils.events import note_events
+        return note_events(self.transcribe(audio), self.sliCQ.midi_freqs, **kwargs)
+
     def reconstruct(self, audio_in):
         """audio (B,1,N) -> re-synthesised audio (B,1,L)."""
         return self.sliCQ.decode(self.chunked_inference(audio_in, False))

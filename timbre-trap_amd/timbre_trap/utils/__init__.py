@@ -25,6 +25,7 @@ from .metrics import (MultipitchEvaluator, multipitch_metrics, multipitch_metric
                       multipitch_metrics_device_track, multipitch_counts_device_track,
                       signal_distortion_ratio, signal_distortion_ratio_device, SignalDistortionRatio)
 from .notes import notes_to_multi_pitch, notes_csr_device, notes_to_activations, note_tiles
+from .events import NoteEvents, note_events, events_to_notes, write_midi
 from .pitch import PitchBank, pitch_to_activations, pitch_tiles
 from .mixing import AudioBank, StemSource, StemMixer, mix_tiles, mix_targets
 from .audio import sinc_resample_kernel, resample_host, resample, mix_resample, prepare_audio
