@@ -438,6 +438,27 @@ int tt_latent16_wgrad_pregated(const float* z, int Dz, float fill, const void* g
                                int E, int T, void* stream);
 int tt_latent16_wgrad(const float* z, int Dz, float fill, const void* g, const void* gy, float* dw, float* db, void* ws, int B,
                       int CT, int D, int E, int T, void* stream);
+/* Decoder.convin over reps (1 or 2) batches of B clips expanded from the SAME latents z (B,Dz,T) -- TimbreTrap.decode_pair: the
+ * reconstruction and the transcription differ only in the constant indicator channel, ind0 in batch 0 and ind1 in batch 1 (Dz = D - 1;
+ * with Dz = D there is no such channel and ind0 / ind1 are ignored).  Clip b of the reps * B clips of out / g / gy belongs to clip
+ * b mod B of z, the convention of tt_skip_join16_fwd's embeddings.  B is the batch of z; ws: tt_latent16_scratch_bytes(reps * B, ...).
+ *   tt_latent16_image_bytes     size of zt, the 16-bit image of z that the forward leaves for the backward (16-byte aligned)
+ *   tt_latent16_expand_reps     out (reps B,CT,E,T) cl16 = ELU(bias + expansion) as tt_latent16_expand (bias != NULL) makes it of the
+ *                               concatenated batch; z is transposed ONCE, into zt (written whole; no indicator in it)
+ *   tt_latent16_contract_reps   out (B,Dout,T) fp32 = sum over the reps batches of the contraction of g, gated by gy where gy != NULL, else
+ *                               g arrives gated (tt_latent16_contract_pregated's meaning and its refusals): each batch accumulated apart,
+ *                               the finished fp32 results added -- the bits of reps calls and an fp32 add
+ *   tt_latent16_wgrad_reps      dw += sum over all reps B clips of z x g, db += sum g, from the image zt of tt_latent16_expand_reps (the
+ *                               same Dz, ind0, ind1, reps); gy as above.  The indicator row of dw takes ind0 / ind1 times its batch's sum;
+ *                               no gradient with respect to the indicator is formed.
+ * reps = 1 gives the results of the entry points above bit for bit. */
+int64_t tt_latent16_image_bytes(int B, int CT, int D, int T);
+int tt_latent16_expand_reps(const float* z, int Dz, float ind0, float ind1, int reps, const float* w, const float* bias, void* out,
+                            void* zt, void* ws, int B, int CT, int D, int E, int T, void* stream);
+int tt_latent16_contract_reps(const void* g, const void* gy, const float* w, float* out, void* ws, int B, int CT, int D, int Dout, int E,
+                              int T, int reps, void* stream);
+int tt_latent16_wgrad_reps(const void* zt, int Dz, float ind0, float ind1, int reps, const void* g, const void* gy, float* dw, float* db,
+                           void* ws, int B, int CT, int D, int E, int T, void* stream);
 
 /* The 3x3 boundary convolutions where fp32 planar tensors meet the bf16 channels-last interior (csrc/conv_edge_bf16.hip), for
  * C0 = 4 first-level channels (model_complexity 2):
@@ -1065,6 +1086,13 @@ int tt_latent16_expand_h(const float* z, int Dz, float fill, const float* w, con
                        int D, int E, int T, void* stream);
 int tt_latent16_wgrad_h(const float* z, int Dz, float fill, const void* g, const void* gy, float* dw, float* db, void* ws, int B,
                       int CT, int D, int E, int T, void* stream);
+int64_t tt_latent16_image_bytes_h(int B, int CT, int D, int T);
+int tt_latent16_expand_reps_h(const float* z, int Dz, float ind0, float ind1, int reps, const float* w, const float* bias, void* out,
+                            void* zt, void* ws, int B, int CT, int D, int E, int T, void* stream);
+int tt_latent16_contract_reps_h(const void* g, const void* gy, const float* w, float* out, void* ws, int B, int CT, int D, int Dout, int E,
+                              int T, int reps, void* stream);
+int tt_latent16_wgrad_reps_h(const void* zt, int Dz, float ind0, float ind1, int reps, const void* g, const void* gy, float* dw, float* db,
+                           void* ws, int B, int CT, int D, int E, int T, void* stream);
 int64_t tt_edge16_scratch_bytes_h(void);
 int tt_convin16_fwd_h(const float* x, const float* w, const float* b, void* y, int B, int H, int T, void* stream);
 int tt_convin16_bwd_h(const float* x, const void* y, const void* dy, const float* w, float* dx, float* dw, float* db, void* ws,

@@ -82,10 +82,17 @@ __global__ __launch_bounds__(NT) void k_lat_zprep(const float* __restrict__ z, e
 // QN = 16-frame groups per wave.  With 4 (a workgroup = 256 frames) the 64-clip step launches 256 workgroups = ONE per CU, and the
 // 62 barrier-separated K steps run with four waves per CU (452 VGPRs at CT = 64: 164 us for 0.52 GB); QN = 1 gives 1024 workgroups
 // of 64 frames, 36 accumulator registers per wave and several workgroups per CU (the weights are re-read from L2).
-template <int CT, int DT, bool GATE, int QN>
-__global__ __launch_bounds__(NT) void k_lat_contract(const e16* __restrict__ in, const e16* __restrict__ gy,
-                                                      const e16* __restrict__ wp, const float* __restrict__ bias,
-                                                      float* __restrict__ out, int D, int Dout, int E, int T, long npix, float oscale) {
+// REPS = 2 (the backward of a pair decode, TimbreTrap.decode_pair): `in` (and gy) hold two batches back to back, `hstride` elements apart,
+// that were expanded from the SAME latents; out = the sum of their two contractions.  A workgroup takes the same frames of BOTH halves
+// through the K steps side by side -- a step's weights are staged once and used twice, two operand requests are in flight per wave -- in
+// separate accumulators, and adds the two finished fp32 results: the values and the order of the two launches and the fp32 add this
+// replaces, bit for bit.  (One half after the other through the same pipeline, 2 x nsteps steps, left half as many requests in flight as
+// the two launches had: 255 us per call against ~207.)
+template <int CT, int DT, bool GATE, int QN, int REPS>
+__device__ __forceinline__ void lat_contract_body(const e16* __restrict__ in, const e16* __restrict__ gy,
+                                                  const e16* __restrict__ wp, const float* __restrict__ bias,
+                                                  float* __restrict__ out, int D, int Dout, int E, int T, long npix, float oscale,
+                                                  long hstride) {
     constexpr int SPH = CT / 32;
     constexpr int CHUNK = DT * 64 * 16, ROUNDS = (DT * 64 + NT - 1) / NT;      // bytes of one step's weights
     extern __shared__ __align__(16) unsigned char smem[];       // two buffers of ROUNDS * NT * 16 bytes
@@ -109,11 +116,11 @@ __global__ __launch_bounds__(NT) void k_lat_contract(const e16* __restrict__ in,
             glds16(src + (long)(p < DT * 64 ? p : DT * 64 - 1) * 8, smem + buf * (ROUNDS * NT * 16) + (long)i * 16);
         }
     };
-    auto fetch = [&](int s, e16x8 (&q8)[QN]) {
+    auto fetch = [&](int s, int rep, e16x8 (&q8)[QN]) {
         const int h = s / SPH, half = s - h * SPH;
 #pragma unroll
         for (int q = 0; q < QN; ++q) {
-            const long off = base[q] + (long)h * T * CT + 32 * half;
+            const long off = base[q] + rep * hstride + (long)h * T * CT + 32 * half;
             const bool live = ok[q] && s < nsteps;
             e16x8 v = *reinterpret_cast<const e16x8*>(in + (live ? off : 0));
             if (GATE) {
@@ -127,28 +134,53 @@ __global__ __launch_bounds__(NT) void k_lat_contract(const e16* __restrict__ in,
             q8[q] = v;
         }
     };
-    f32x4 acc[DT][QN];
+    f32x4 acc[REPS][DT][QN];
 #pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
+    for (int rp = 0; rp < REPS; ++rp)
 #pragma unroll
-        for (int q = 0; q < QN; ++q) acc[dt][q] = f32x4{0.f, 0.f, 0.f, 0.f};
-    e16x8 bq[QN], bn[QN];
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int q = 0; q < QN; ++q) acc[rp][dt][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    e16x8 bq[REPS][QN], bn[REPS][QN];
     stage(0, 0);
-    fetch(0, bq);
+#pragma unroll
+    for (int rp = 0; rp < REPS; ++rp) fetch(0, rp, bq[rp]);
     for (int s = 0; s < nsteps; ++s) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this step's weights (and operands) have landed
         __syncthreads();                                         // ... for every wave; the other buffer is free again
         if (s + 1 < nsteps) stage(s + 1, (s + 1) & 1);
-        fetch(s + 1, bn);
+#pragma unroll
+        for (int rp = 0; rp < REPS; ++rp) fetch(s + 1, rp, bn[rp]);
         const unsigned char* wb = smem + (s & 1) * (ROUNDS * NT * 16);
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
             const e16x8 a = *reinterpret_cast<const e16x8*>(wb + ((long)dt * 64 + lane) * 16);
 #pragma unroll
-            for (int q = 0; q < QN; ++q) acc[dt][q] = mma32(a, bq[q], acc[dt][q]);
+            for (int rp = 0; rp < REPS; ++rp)
+#pragma unroll
+                for (int q = 0; q < QN; ++q) acc[rp][dt][q] = mma32(a, bq[rp][q], acc[rp][dt][q]);
         }
 #pragma unroll
-        for (int q = 0; q < QN; ++q) bq[q] = bn[q];
+        for (int rp = 0; rp < REPS; ++rp)
+#pragma unroll
+            for (int q = 0; q < QN; ++q) bq[rp][q] = bn[rp][q];
+    }
+    // The bias of the lane's DT * 4 output rows goes through the LDS, free now: one read per thread, ONE wait for memory, then 16-byte LDS
+    // reads.  Read inside the guarded stores each element waited out a memory latency of its own before the next was requested (36 in a
+    // row at CT = 64).  Registers of k_lat_contract<64, 9, *, 1>, vector + accumulator together as the occupancy counts them: 88 with the
+    // serial reads, 124 in this form (the epilogue holds 36 bias values next to the 36 sums), 144 with the 36 values read from memory in
+    // one batch, in front of the K loop or behind it -- four waves per SIMD still fit 124, not 144.
+    static_assert(16 * DT <= NT, "one thread per bias element");
+    f32x4 bv[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) bv[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (REPS == 1 && bias) {
+        float* bl = reinterpret_cast<float*>(smem);
+        __syncthreads();                                         // every wave is done with the weights
+        if (tid < 16 * DT) bl[tid] = tid < Dout ? bias[tid] : 0.f;
+        __syncthreads();
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) bv[dt] = *reinterpret_cast<const f32x4*>(bl + 16 * dt + 4 * g);
     }
 #pragma unroll
     for (int q = 0; q < QN; ++q) {
@@ -159,10 +191,29 @@ __global__ __launch_bounds__(NT) void k_lat_contract(const e16* __restrict__ in,
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int d = 16 * dt + 4 * g + r;
-                if (d < Dout) out[(b * Dout + d) * T + t] = acc[dt][q][r] * oscale + (bias ? bias[d] : 0.f);
+                if constexpr (REPS == 2) {                       // each half as the one-batch form finishes it, then the add autograd made
+                    if (d < Dout) out[(b * Dout + d) * T + t] = __fadd_rn(__fadd_rn(__fmul_rn(acc[0][dt][q][r], oscale), 0.f),
+                                                                          __fadd_rn(__fmul_rn(acc[REPS - 1][dt][q][r], oscale), 0.f));
+                } else {
+                    if (d < Dout) out[(b * Dout + d) * T + t] = acc[0][dt][q][r] * oscale + bv[dt][r];
+                }
             }
     }
-    (void)CHUNK;
+    (void)CHUNK; (void)D;
+}
+
+template <int CT, int DT, bool GATE, int QN>
+__global__ __launch_bounds__(NT) void k_lat_contract(const e16* __restrict__ in, const e16* __restrict__ gy,
+                                                      const e16* __restrict__ wp, const float* __restrict__ bias,
+                                                      float* __restrict__ out, int D, int Dout, int E, int T, long npix, float oscale) {
+    lat_contract_body<CT, DT, GATE, QN, 1>(in, gy, wp, bias, out, D, Dout, E, T, npix, oscale, 0);
+}
+// the two halves of a pair decode's gradient contracted and summed (lat_contract_body, REPS = 2); npix = the pixels of ONE half
+template <int CT, int DT, bool GATE, int QN>
+__global__ __launch_bounds__(NT) void k_lat_contract2(const e16* __restrict__ in, const e16* __restrict__ gy,
+                                                       const e16* __restrict__ wp, float* __restrict__ out, int D, int Dout, int E, int T,
+                                                       long npix, float oscale, long hstride) {
+    lat_contract_body<CT, DT, GATE, QN, 2>(in, gy, wp, nullptr, out, D, Dout, E, T, npix, oscale, hstride);
 }
 
 // ---- expand to (h, c) ----------------------------------------------------------------------------------------------------------
@@ -170,10 +221,13 @@ __global__ __launch_bounds__(NT) void k_lat_contract(const e16* __restrict__ in,
 // 2 gives 512 workgroups with half the accumulators.
 // GOUT (backward use, !ACT): out = (.) * ELU'(gy) with gy the saved output of the layer in front (Encoder's last strided layer), whose
 // backward then takes the gradient already gated (tt_sconv16_bwd_pregated)
+// nsrc / prow / ind0, ind1 (the pair form, tt_latent16_expand_reps): zt holds nsrc pixels and output pixel p reads pixel p mod nsrc of it
+// (p < 2 nsrc: the clips of a 2 B batch read the image of clip b mod B, like the skip join's embeddings); row prow >= 0 of the operand is
+// the constant ind0 for p < nsrc and ind1 behind -- the indicator channel of TimbreTrap.decode_pair, which the image does not carry
 template <int CT, int KS, bool ACT, int QE, bool GOUT = false>
 __global__ __launch_bounds__(NT) void k_lat_expand(const e16* __restrict__ zt, const e16* __restrict__ wp,
                                                     const float* __restrict__ bias, e16* __restrict__ out, int E, int T,
-                                                    long npix, const e16* __restrict__ gy = nullptr) {
+                                                    long npix, const e16* __restrict__ gy, long nsrc, int prow, float ind0, float ind1) {
     constexpr int NC = CT / 16, NCH = CT / 4, ZS = 32 * KS + 16;
     constexpr int PCS = NC * KS * 64, ROUNDS = (PCS + NT - 1) / NT;            // 16-byte pieces of one row's weights
     extern __shared__ __align__(16) unsigned char smem[];
@@ -187,8 +241,17 @@ __global__ __launch_bounds__(NT) void k_lat_expand(const e16* __restrict__ zt, c
         const long pix = p0 + 16 * q + n;
         ok[q] = pix < npix;
         const long pc = ok[q] ? pix : 0;
+        const long ps = pc >= nsrc ? pc - nsrc : pc;
 #pragma unroll
-        for (int s = 0; s < KS; ++s) bz[q][s] = *reinterpret_cast<const e16x8*>(zt + pc * ZS + 32 * s + 8 * g);
+        for (int s = 0; s < KS; ++s) bz[q][s] = *reinterpret_cast<const e16x8*>(zt + ps * ZS + 32 * s + 8 * g);
+        if (prow >= 0) {
+            const e16 iv = (e16)(pc >= nsrc ? ind1 : ind0);
+#pragma unroll
+            for (int s = 0; s < KS; ++s)
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    if (32 * s + 8 * g + e == prow) bz[q][s][e] = iv;
+        }
         const long b = pc / T, t = pc - b * T;
         obase[q] = (b * E * T + t) * CT + NCH * g;
     }
@@ -243,12 +306,19 @@ __global__ __launch_bounds__(NT) void k_lat_expand(const e16* __restrict__ zt, c
 }
 
 // ---- weight gradient ------------------------------------------------------------------------------------------------------------
+constexpr bool lat_pieces_distinct(int nt, int per_pixel, int rounds) {
+    for (int r = 1; r < rounds; ++r)
+        if ((nt * r) % per_pixel == 0) return false;
+    return true;
+}
+
 template <int CT> __device__ __forceinline__ int gswz(int p) { return CT == 64 ? ((p >> 1) & 3) : ((p >> 2) & 1); }
 
 template <int CT, int DT, int KS, bool GATE>
 __global__ __launch_bounds__(NT, LAT_WGRAD_WAVES) void k_lat_wgrad(const e16* __restrict__ zt, const e16* __restrict__ g_in,
                                                    const e16* __restrict__ gy, float* __restrict__ part,
-                                                   float* __restrict__ dbpart, int E, int T, long npix, int nsplit) {
+                                                   float* __restrict__ dbpart, int E, int T, long npix, int nsplit, int nsrc, int prow,
+                                                   float ind0, float ind1) {
     constexpr int NC = CT / 16, ZS = 32 * KS + 16, ZB = ZS * 2, GB = CT * 2;   // bytes per pixel of the two images
     constexpr int ZPC = 64 * ZB / 16, GPC = 64 * GB / 16;                      // pieces per 64-pixel chunk
     constexpr int ZR = (ZPC + NT - 1) / NT, GR = (GPC + NT - 1) / NT;
@@ -269,17 +339,43 @@ __global__ __launch_bounds__(NT, LAT_WGRAD_WAVES) void k_lat_wgrad(const e16* __
     // pixel's offset and wraps once (T >= 64) -- the per-piece 64-bit division pixel / T this replaces was most of the staging's
     // ~400 vector instructions per chunk, next to 18 matrix instructions of work (npix < 2^31: checked by the launcher).
     const int npx = (int)npix, nchunks = (npx + 63) / 64;
+    // which of the pieces this thread stages holds the indicator row (prow >= 0: tt_latent16_wgrad_reps), and of which pixel of the chunk:
+    // at most one -- a thread's pieces lie NT apart and NT r is no multiple of the ZB / 16 pieces of a pixel for 0 < r < ZR
+    static_assert(lat_pieces_distinct(NT, ZB / 16, ZR), "a thread stages two pieces of the same position in a pixel");
+    int ipiece = -1, ipix = 0;
+    if (prow >= 0) {
+#pragma unroll
+        for (int r = 0; r < ZR; ++r) {
+            const int p = r * NT + tid, q = p / (ZB / 16);
+            if (p < ZPC && p - q * (ZB / 16) == (prow >> 3)) { ipiece = p; ipix = q; }
+        }
+    }
     for (int ck = ps; ck < nchunks; ck += nsplit) {
         const int px0 = ck * 64;
         const int b0 = px0 / T, t00 = px0 - b0 * T;
         __syncthreads();
         const bool full = px0 + 64 <= npx;                        // every chunk but possibly the last
-        const e16* zc = zt + (long)px0 * ZS;
+        // zt holds nsrc pixels, pixel px of g reads pixel px mod nsrc of it (px < 2 nsrc): the image the forward made of the B clips serves
+        // both halves of a pair decode's batch (tt_latent16_wgrad_reps).  A chunk inside one half is one contiguous run of the image, as
+        // every chunk was before the pair form; only a chunk that spans the two halves (nsrc no multiple of 64) looks up each piece's pixel.
+        // (That branch also takes the ragged last chunk of a ONE-batch call, npx = nsrc: px0 < nsrc < px0 + 64.  okp keeps px < npx = nsrc
+        // there, so px - nsrc is never formed; one chunk per launch.)
+        if (px0 + 64 <= nsrc || px0 >= nsrc) {
+            const e16* zc = zt + (long)(px0 >= nsrc ? px0 - nsrc : px0) * ZS;
 #pragma unroll
-        for (int r = 0; r < ZR; ++r) {                           // zt rows of the chunk are one contiguous run
-            const int i = r * NT + wave * 64, p = i + lane;
-            const bool okp = p < ZPC && (full || px0 + p * 16 / ZB < npx);
-            glds16(okp ? zc + p * 8 : zero, zs + (long)i * 16);
+            for (int r = 0; r < ZR; ++r) {
+                const int i = r * NT + wave * 64, p = i + lane;
+                const bool okp = p < ZPC && (full || px0 + p * 16 / ZB < npx);
+                glds16(okp ? zc + p * 8 : zero, zs + (long)i * 16);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < ZR; ++r) {
+                const int i = r * NT + wave * 64, p = i + lane;
+                const int q = p / (ZB / 16), px = px0 + q;
+                const bool okp = p < ZPC && (full || px < npx);
+                glds16(okp ? zt + (long)(px >= nsrc ? px - nsrc : px) * ZS + (p - q * (ZB / 16)) * 8 : zero, zs + (long)i * 16);
+            }
         }
         e16x8 v[GATE ? GR : 1], yv[GATE ? GR : 1];
 #pragma unroll
@@ -311,6 +407,10 @@ __global__ __launch_bounds__(NT, LAT_WGRAD_WAVES) void k_lat_wgrad(const e16* __
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // the indicator row, which the image does not carry: ind0 in the first nsrc pixels, ind1 behind.  A thread overwrites it in the piece
+        // it staged itself (landed: the wait above), in front of the barrier that publishes the chunk
+        if (ipiece >= 0 && px0 + ipix < npx)
+            *reinterpret_cast<e16*>(zs + (long)ipiece * 16 + 2 * (prow & 7)) = (e16)(px0 + ipix >= nsrc ? ind1 : ind0);
         __syncthreads();
         for (int sub = sub0; sub < 2; sub += WPS) {              // 32-pixel halves of the chunk
             s16x4 lo, hi;
@@ -424,6 +524,27 @@ int run_contract(const e16* in, const e16* gy, const float* w, const float* bias
     return 0;
 }
 
+// the backward of a pair decode: in / gy hold 2 B clips, out (B,Dout,T) = the sum of the two halves' contractions (k_lat_contract2)
+template <int CT, int DT, int KS, bool GATE>
+int run_contract2(const e16* in, const e16* gy, const float* w, float* out, unsigned char* ws, int B, int D, int Dout, int E, int T,
+                  hipStream_t st) {
+    using L = LatSizes<CT, DT, KS>;
+    const long npix = (long)B * T;
+    e16* wp = reinterpret_cast<e16*>(ws);
+    const int pieces = E * L::SPH * DT * 64;
+    hipLaunchKernelGGL((k_lat_wprep1<CT, DT>), dim3((pieces + NT - 1) / NT), dim3(NT), 0, st, w, wp, D, E);
+    TT_LAUNCH_CHECK();
+    constexpr int ROUNDS = (DT * 64 + NT - 1) / NT, LDS = 2 * ROUNDS * NT * 16;
+    static AttrOnce once;
+    constexpr int QN = CT == 64 ? TT_LAT_QN64 : 4;
+    auto kern = k_lat_contract2<CT, DT, GATE, QN>;
+    if (int rc = raise_lds(kern, LDS, once)) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((npix + 64 * QN - 1) / (64 * QN))), dim3(NT), LDS, st, in, gy, wp, out, D, Dout, E, T, npix,
+                       tt_loss_unscale(), (long)B * E * T * CT);
+    TT_LAUNCH_CHECK();
+    return 0;
+}
+
 template <int CT, int DT, int KS, bool ACT, bool GOUT = false>
 int run_expand(const float* z, int Dz, float fill, const float* w, const float* bias, e16* out, unsigned char* ws, int B, int D, int E,
                int T, hipStream_t st, const e16* gy = nullptr) {
@@ -444,10 +565,45 @@ int run_expand(const float* z, int Dz, float fill, const float* w, const float* 
     constexpr int QE = LAT_EXPAND_Q;
     auto kern = k_lat_expand<CT, KS, ACT, QE, GOUT>;
     if (int rc = raise_lds(kern, LDS, once)) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((npix + 64 * QE - 1) / (64 * QE))), dim3(NT), LDS, st, zt, wp, bias, out, E, T, npix, gy);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((npix + 64 * QE - 1) / (64 * QE))), dim3(NT), LDS, st, zt, wp, bias, out, E, T, npix, gy, npix, -1,
+                       0.f, 0.f);
     TT_LAUNCH_CHECK();
     return 0;
 }
+
+// The forward of Decoder.convin that keeps its operand: zt (tt_latent16_image_bytes) receives the bf16 image of the B clips of z -- WITHOUT
+// the indicator row (row Dz is 0 there; the kernels that read the image put the half's value in) and with the weight gradient's row of
+// ones at row D where the tile has one (D < 16 DT) -- and out = reps batches of B clips expanded from it, batch r with the indicator ind[r].
+// The row of ones is written for every backward, not only the pregated one that reads it (the one-batch run_wgrad writes it only then): the
+// forward does not know which backward follows.  It costs nothing elsewhere: k_lat_wprep2 zero-fills the weight rows >= D that meet it in the
+// expansion, and the gated weight gradient's k_lat_wred drops rows >= D (db_row = -1).
+template <int CT, int DT, int KS>
+int run_expand_reps(const float* z, int Dz, float ind0, float ind1, int reps, const float* w, const float* bias, e16* out, e16* zt,
+                    unsigned char* ws, int B, int D, int E, int T, hipStream_t st) {
+    using L = LatSizes<CT, DT, KS>;
+    const long nsrc = (long)B * T, npix = reps * nsrc;
+    e16* wp = reinterpret_cast<e16*>(ws);
+    const int pieces = E * L::NC * KS * 64;
+    hipLaunchKernelGGL((k_lat_wprep2<CT, KS>), dim3((pieces + NT - 1) / NT), dim3(NT), 0, st, w, wp, D, E);
+    TT_LAUNCH_CHECK();
+    const long zp = ((nsrc + 63) / 64) * 64 * (L::ZS / 8);
+    hipLaunchKernelGGL((k_lat_zprep<KS>), dim3((unsigned)((zp + NT - 1) / NT)), dim3(NT), 0, st, z, zt, D, Dz, 0.f, T, nsrc, 1.f,
+                       D < 16 * DT ? D : -1);
+    TT_LAUNCH_CHECK();
+    constexpr int PCS = L::NC * KS * 64, ROUNDS = (PCS + NT - 1) / NT, LDS = 2 * ROUNDS * NT * 16;
+    static AttrOnce once;
+    constexpr int QE = LAT_EXPAND_Q;
+    auto kern = k_lat_expand<CT, KS, true, QE, false>;
+    if (int rc = raise_lds(kern, LDS, once)) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((npix + 64 * QE - 1) / (64 * QE))), dim3(NT), LDS, st, zt, wp, bias, out, E, T, npix,
+                       (const e16*)nullptr, nsrc, Dz < D ? Dz : -1, ind0, ind1);
+    TT_LAUNCH_CHECK();
+    return 0;
+}
+
+template <int CT, int DT, int KS, bool GATE>
+int wgrad_from_image(const e16* zt, long nsrc, int prow, float ind0, float ind1, const e16* g_in, const e16* gy, float* dw, float* db,
+                     float* part, float* dbpart, int B, int D, int E, int T, hipStream_t st, bool pregated);
 
 template <int CT, int DT, int KS, bool GATE>
 int run_wgrad(const float* z, int Dz, float fill, const e16* g_in, const e16* gy, float* dw, float* db, unsigned char* ws, int B,
@@ -468,13 +624,26 @@ int run_wgrad(const float* z, int Dz, float fill, const e16* g_in, const e16* gy
     hipLaunchKernelGGL((k_lat_zprep<KS>), dim3((unsigned)((zp + NT - 1) / NT)), dim3(NT), 0, st, z, zt, D, Dz, fill, T, npix,
                        (GATE || pregated) ? 1.f : tt_loss_scale(), one_row);
     TT_LAUNCH_CHECK();
+    return wgrad_from_image<CT, DT, KS, GATE>(zt, npix, -1, 0.f, 0.f, g_in, gy, dw, db, part, dbpart, B, D, E, T, st, pregated);
+}
+
+// the weight gradient from a prepared image of nsrc pixels that the B T >= nsrc pixels of g read at pixel mod nsrc (k_lat_wgrad), row prow
+// of it the constants ind0 / ind1; tt_latent16_wgrad_reps hands over the image the forward kept (run_expand_reps)
+template <int CT, int DT, int KS, bool GATE>
+int wgrad_from_image(const e16* zt, long nsrc, int prow, float ind0, float ind1, const e16* g_in, const e16* gy, float* dw, float* db,
+                     float* part, float* dbpart, int B, int D, int E, int T, hipStream_t st, bool pregated) {
+    const long npix = (long)B * T;
+    if (npix >= (1l << 30) || (long)B * E * T >= (1l << 31) || npix > 2 * nsrc) return TT_E_UNSUPPORTED;
+    if (pregated && (GATE || D >= 16 * DT || !db)) return TT_E_UNSUPPORTED;
+    const int one_row = pregated ? D : -1;
+    using L = LatSizes<CT, DT, KS>;
     constexpr int ZB = L::ZS * 2, GBY = CT * 2;
     constexpr int ZR = (64 * ZB / 16 + NT - 1) / NT, GR = (64 * GBY / 16 + NT - 1) / NT;
     constexpr int LDS0 = (ZR + GR) * NT * 16, LDS = LDS0 > NT * 32 ? LDS0 : NT * 32;
     static AttrOnce once;
     auto kern = k_lat_wgrad<CT, DT, KS, GATE>;
     if (int rc = raise_lds(kern, LDS, once)) return rc;
-    hipLaunchKernelGGL(kern, dim3(E * NSPLIT), dim3(NT), LDS, st, zt, g_in, gy, part, dbpart, E, T, npix, NSPLIT);
+    hipLaunchKernelGGL(kern, dim3(E * NSPLIT), dim3(NT), LDS, st, zt, g_in, gy, part, dbpart, E, T, npix, NSPLIT, (int)nsrc, prow, ind0, ind1);
     TT_LAUNCH_CHECK();
     const int total = E * (CT / 16) * DT * 256 + CT * 16;
     // (pregated: dbpart, unused by that form's weight-gradient kernel, holds the E x CT row sums between the two stages)
@@ -609,6 +778,74 @@ int tt_latent16_wgrad_pregated(const float* z, int Dz, float fill, const void* g
     switch (cfg_of(CT, D)) {
         case 1: return run_wgrad<32, 3, 2, false>(z, Dz, fill, (const e16*)g, nullptr, dw, db, (unsigned char*)ws, B, D, E, T, st, true);
         case 2: return run_wgrad<64, 9, 5, false>(z, Dz, fill, (const e16*)g, nullptr, dw, db, (unsigned char*)ws, B, D, E, T, st, true);
+    }
+    return TT_E_UNSUPPORTED;
+}
+
+/* The pair forms (TimbreTrap.decode_pair; include/ttrap.h): Decoder.convin over reps batches of B clips that share their latents.  The
+ * forward keeps the 16-bit image of the latents in zt for the weight gradient; the image carries no indicator, each use names the halves'. */
+int64_t tt_latent16_image_bytes(int B, int CT, int D, int T) {
+    const long npix = (long)B * T;
+    switch (cfg_of(CT, D)) {
+        case 1: return LatSizes<32, 3, 2>::zt_bytes(npix);
+        case 2: return LatSizes<64, 9, 5>::zt_bytes(npix);
+    }
+    return -1;
+}
+
+int tt_latent16_expand_reps(const float* z, int Dz, float ind0, float ind1, int reps, const float* w, const float* bias, void* out,
+                            void* zt, void* ws, int B, int CT, int D, int E, int T, void* stream) {
+    if (!z || !w || !bias || !out || !zt || !ws || B <= 0 || E <= 0 || T <= 0 || T % 16 || (Dz != D && Dz != D - 1) || (reps != 1 && reps != 2))
+        return TT_E_BADARG;
+    if (!lat_aligned(out, zt, ws)) return TT_E_BADARG;
+    hipStream_t st = tt_stream(stream);
+    switch (cfg_of(CT, D)) {
+        case 1: return run_expand_reps<32, 3, 2>(z, Dz, ind0, ind1, reps, w, bias, (e16*)out, (e16*)zt, (unsigned char*)ws, B, D, E, T, st);
+        case 2: return run_expand_reps<64, 9, 5>(z, Dz, ind0, ind1, reps, w, bias, (e16*)out, (e16*)zt, (unsigned char*)ws, B, D, E, T, st);
+    }
+    return TT_E_UNSUPPORTED;
+}
+
+int tt_latent16_contract_reps(const void* g, const void* gy, const float* w, float* out, void* ws, int B, int CT, int D, int Dout, int E,
+                              int T, int reps, void* stream) {
+    if (!g || !w || !out || !ws || B <= 0 || E <= 0 || T <= 0 || T % 16 || Dout < 1 || Dout > D || (reps != 1 && reps != 2)) return TT_E_BADARG;
+    if (!lat_aligned(g, gy, ws)) return TT_E_BADARG;
+    if (reps == 1)
+        return gy ? tt_latent16_contract(g, gy, w, nullptr, out, ws, B, CT, D, Dout, E, T, stream)
+                  : tt_latent16_contract_pregated(g, w, out, ws, B, CT, D, Dout, E, T, stream);
+    hipStream_t st = tt_stream(stream);
+    const e16 *i = (const e16*)g, *y = (const e16*)gy;
+    unsigned char* s = (unsigned char*)ws;
+    const int cfg = cfg_of(CT, D);
+    if (!gy && !tt_latent16_pregated_ok(CT, D)) return TT_E_UNSUPPORTED;     // like tt_latent16_contract_pregated
+    switch (cfg) {
+        case 1: return y ? run_contract2<32, 3, 2, true>(i, y, w, out, s, B, D, Dout, E, T, st) : run_contract2<32, 3, 2, false>(i, y, w, out, s, B, D, Dout, E, T, st);
+        case 2: return y ? run_contract2<64, 9, 5, true>(i, y, w, out, s, B, D, Dout, E, T, st) : run_contract2<64, 9, 5, false>(i, y, w, out, s, B, D, Dout, E, T, st);
+    }
+    return TT_E_UNSUPPORTED;
+}
+
+int tt_latent16_wgrad_reps(const void* zt, int Dz, float ind0, float ind1, int reps, const void* g, const void* gy, float* dw, float* db,
+                           void* ws, int B, int CT, int D, int E, int T, void* stream) {
+    if (!zt || !g || !dw || !db || !ws || B <= 0 || E <= 0 || T <= 0 || T % 16 || (Dz != D && Dz != D - 1) || (reps != 1 && reps != 2))
+        return TT_E_BADARG;
+    if (!lat_aligned(zt, g, gy, ws)) return TT_E_BADARG;
+    hipStream_t st = tt_stream(stream);
+    const e16 *gi = (const e16*)g, *y = (const e16*)gy, *zi = (const e16*)zt;
+    const long nsrc = (long)B * T;
+    const int prow = Dz < D ? Dz : -1, Bg = reps * B;
+    float* part = (float*)ws;
+    switch (cfg_of(CT, D)) {
+        case 1: {
+            float* dbpart = part + (long)NSPLIT * E * 4 * 3 * 256;
+            return y ? wgrad_from_image<32, 3, 2, true>(zi, nsrc, prow, ind0, ind1, gi, y, dw, db, part, dbpart, Bg, D, E, T, st, false)
+                     : wgrad_from_image<32, 3, 2, false>(zi, nsrc, prow, ind0, ind1, gi, y, dw, db, part, dbpart, Bg, D, E, T, st, true);
+        }
+        case 2: {
+            float* dbpart = part + (long)NSPLIT * E * 4 * 9 * 256;
+            return y ? wgrad_from_image<64, 9, 5, true>(zi, nsrc, prow, ind0, ind1, gi, y, dw, db, part, dbpart, Bg, D, E, T, st, false)
+                     : wgrad_from_image<64, 9, 5, false>(zi, nsrc, prow, ind0, ind1, gi, y, dw, db, part, dbpart, Bg, D, E, T, st, true);
+        }
     }
     return TT_E_UNSUPPORTED;
 }

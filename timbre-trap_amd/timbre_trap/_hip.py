@@ -148,6 +148,10 @@ _PROTOS = {
     'tt_latent16_contract': (c_int, [P, P, P, P, P, P, I, I, I, I, I, I, P]),
     'tt_latent16_expand': (c_int, [P, I, F_, P, P, P, P, I, I, I, I, I, P]),
     'tt_latent16_wgrad': (c_int, [P, I, F_, P, P, P, P, P, I, I, I, I, I, P]),
+    'tt_latent16_image_bytes': (c_int64, [I, I, I, I]),
+    'tt_latent16_expand_reps': (c_int, [P, I, F_, F_, I, P, P, P, P, P, I, I, I, I, I, P]),
+    'tt_latent16_contract_reps': (c_int, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    'tt_latent16_wgrad_reps': (c_int, [P, I, F_, F_, I, P, P, P, P, P, I, I, I, I, I, P]),
     'tt_edge16_scratch_bytes': (c_int64, []),
     'tt_convin16_fwd': (c_int, [P, P, P, P, I, I, I, P]),
     'tt_convin16_bwd': (c_int, [P, P, P, P, P, P, P, P, I, I, I, P]),
@@ -236,7 +240,8 @@ _PROTOS = {
 HALF_TWINS = ('tt_wide_level_scratch_bytes', 'tt_wide_level_bwd', 'tt_wide_level_bwd_gated', 'tt_wide_level_bwd_gated_join', 'tt_gate16', 'tt_latent16_pregated_ok', 'tt_latent16_expand_gated', 'tt_latent16_contract_pregated', 'tt_latent16_wgrad_pregated', 'tt_sconv16_bwd_pregated', 'tt_tconv16_bwd_pregated', 'tt_wide_scratch_bytes', 'tt_wide_pack', 'tt_wide_unpack', 'tt_wide_rb_fwd', 'tt_wide_rb_fwd_join', 'tt_wide_rb_bwd', 'tt_wide_fused_scratch_bytes',
               'tt_wide_rb_bwd_fused', 'tt_wide_onepass_scratch_bytes', 'tt_wide_rb_bwd_onepass', 'tt_wide_rb_bwd_is_onepass', 'tt_wide_bwd_kernel_attr',
               'tt_stride16_scratch_bytes', 'tt_sconv16_fwd', 'tt_sconv16_bwd', 'tt_tconv16_fwd', 'tt_tconv16_bwd', 'tt_latent16_scratch_bytes',
-              'tt_latent16_contract', 'tt_latent16_expand', 'tt_latent16_wgrad', 'tt_edge16_scratch_bytes', 'tt_convin16_fwd', 'tt_convin16_bwd',
+              'tt_latent16_contract', 'tt_latent16_expand', 'tt_latent16_wgrad', 'tt_latent16_image_bytes', 'tt_latent16_expand_reps',
+              'tt_latent16_contract_reps', 'tt_latent16_wgrad_reps', 'tt_edge16_scratch_bytes', 'tt_convin16_fwd', 'tt_convin16_bwd',
               'tt_convout16_fwd', 'tt_convout16_bwd', 'tt_convin16_1_fwd', 'tt_convin16_1_bwd', 'tt_convout16_1_fwd', 'tt_convout16_1_bwd',
               'tt_scaled_add16', 'tt_dot16', 'tt_skip_join16_fwd', 'tt_skip_join16_bwd')
 for _n in HALF_TWINS:

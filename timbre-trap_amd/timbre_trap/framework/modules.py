@@ -204,7 +204,8 @@ class Decoder(nn.Module):
 
     def forward(self, latents, encoder_embeddings=None, indicator=None, pair=False, act=ACT_NONE):
         """``indicator``: None (latents carry the switch channel, the reference's call) or its constant value (then latents have
-        one channel less and ops.latent_decode supplies it).  ``pair`` (TimbreTrap.decode_pair): the batch is two batches back to
+        one channel less and ops.latent_decode supplies it), or with ``pair`` the values of the two halves, which are then both decoded
+        from the one batch of latents.  ``pair`` (TimbreTrap.decode_pair): the batch is two batches back to
         back; returns their two logits tensors.  ``encoder_embeddings``: the scaled embeddings (reference modules.py:569-589) or
         ops.SkipJoin descriptors (TimbreTrap.skip_joins: weight and join in one pass; with ``pair`` each serves both halves).
         ``act``: a nonlinearity behind convout, applied in its epilogue (the magnitude variants' decode: TimbreTrap.OUT_ACT)."""
@@ -296,9 +297,9 @@ class TimbreTrap(nn.Module):
         TTRAP_PAIR_DECODE=0 / TimbreTrap.PAIR_DECODE = False: two passes."""
         joins = embeddings is not None and all(isinstance(e, ops.SkipJoin) and ops.is_cl16(e.e) for e in embeddings)
         if self.PAIR_DECODE and (embeddings is None or joins) and ops.cl16_mode() and torch.is_grad_enabled() and latents.dim() == 3:
-            ones = torch.ones_like(latents[..., :1, :])
-            z = torch.cat((torch.cat((latents, ones), dim=-2), torch.cat((latents, torch.zeros_like(ones)), dim=-2)), dim=0)
-            return self.decoder(z, embeddings, pair=True, act=self.OUT_ACT)
+            # the latents as they are: the 16-bit latent head expands both halves from them, each with its indicator as a constant channel,
+            # and its backward returns the sum of the halves' gradients (ops.LatDec16Fn ``pair``) -- no concatenated copies
+            return self.decoder(latents, embeddings, indicator=(1.0, 0.0), pair=True, act=self.OUT_ACT)
         return self.decode(latents, embeddings), self.decode(latents, embeddings, True)
 
     def _inference(self, audio, transcribe=False, check=True):

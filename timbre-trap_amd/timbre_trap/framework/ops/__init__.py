@@ -379,10 +379,18 @@ def latent_encode(top, w, b, link=None):
 def latent_decode(z, w, b, fill=None, out_x3=False, link=None):
     """
     Decoder.convin (modules.py:534) + ELU; cl16 output in the bf16 mode.  ``fill``: value of a constant last input channel that z
-    does not carry (see LatDec16Fn); on the fp32 path the channel is concatenated like the reference does.  ``out_x3`` (inside
+    does not carry (see LatDec16Fn); on the fp32 path the channel is concatenated like the reference does.  A PAIR of values
+    (TimbreTrap.decode_pair): the output is two batches back to back, the first decoded with fill[0] and the second with fill[1] -- inside
+    the 16-bit head (LatDec16Fn ``pair``); elsewhere the two batches are concatenated first.  ``out_x3`` (inside
     ops.x3_chain_scope): the next layer takes a split-operand tensor.
     """
     Dz = z.size(1) + (fill is not None)
+    if isinstance(fill, (tuple, list)):
+        if (cl16_mode() and FUSED_RESBLOCK and _f32ok(w) and z.dim() == 3 and z.is_cuda and w.size(0) == Dz and w.size(3) == 1
+                and not (out_x3 and x3_chain()) and _lat16_ok(w.size(1), w.size(0), w.size(2), z.size(2), b)):
+            return LatDec16Fn.apply(z, w, b, None, link, (float(fill[0]), float(fill[1])))
+        z = torch.cat([torch.cat((z, torch.full_like(z[..., :1, :], float(v))), dim=-2) for v in fill], dim=0)
+        fill = None
     if (out_x3 and x3_chain() and z.dim() == 3 and z.is_cuda and w.size(0) == Dz and x3_latent_ok(w.size(1), Dz - 1, w_dec=w)
             and w.size(2) * w.size(1) * 4 + 2 * ((Dz - 1) // 32) * (w.size(1) // 16) * 2048 <= 160 * 1024):
         return x3_latent_decode(z, w, b, fill, True)

@@ -365,49 +365,56 @@ class LatDec16Fn(torch.autograd.Function):
     Decoder.convin producing the cl16 top embedding: z (B,Dz,T) fp32 -> ELU(tconv) (B,CT,E,T) cl16.  ``fill`` is None (z carries
     all D = w.size(0) input channels) or the value of a constant LAST channel that z does not carry (Dz = D - 1): the
     transcription switch of TimbreTrap.decode (reference modules.py:139-142) without building the concatenated tensor.
+    ``pair`` = (i0, i1) (TimbreTrap.decode_pair; then ``fill`` is None): the output is two batches back to back, both expanded from z,
+    the first with the constant channel i0 and the second with i1 (tt_latent16_expand_reps); the backward sums the two halves' latent
+    gradient inside the contraction and returns one (B,Dz,T) tensor -- no concatenated copies of the latents, no sliced cat backward and
+    no add.  Either way z is transposed to 16 bits once, in the forward; the backward's weight gradient reads that image.
     """
 
     @staticmethod
-    def forward(ctx, z, w, b, fill, link=None):
+    def forward(ctx, z, w, b, fill, link=None, pair=None):
         z = _f32c(z)
         B, Dz, T = z.shape
         D, CT, E = w.size(0), w.size(1), w.size(2)
+        if pair is not None and (fill is not None or Dz != D - 1):
+            raise ValueError('LatDec16Fn: a pair decode takes the latents without the indicator channel and no fill')
+        ctx.reps = 1 if pair is None else 2
+        ctx.ind = (0.0 if fill is None else float(fill),) * 2 if pair is None else (float(pair[0]), float(pair[1]))
+        R = ctx.reps
         # the pregated backward carries the bias gradient in a free input row of the weight gradient: the library says where it can
         ctx.link = link if (link is not None and lib16(_ops.cl16_dtype()).tt_latent16_pregated_ok(CT, D)) else None
         if ctx.link is not None:
             ctx.link.producer = True
-        y = new_cl16(B, CT, E, T, z.device, _ops.cl16_dtype())
+        y = new_cl16(R * B, CT, E, T, z.device, _ops.cl16_dtype())
         lib = lib16(y)
-        ws = torch.empty(lib.tt_latent16_scratch_bytes(B, CT, D, E, T), dtype=torch.uint8, device=z.device)
-        ctx.fill = 0.0 if fill is None else float(fill)
-        check(lib.tt_latent16_expand(ptr(z), Dz, ctx.fill, ptr(w), ptr(b), ptr(y), ptr(ws), B, CT, D, E, T, stream_ptr()),
-              'tt_latent16_expand')
+        ws = torch.empty(lib.tt_latent16_scratch_bytes(R * B, CT, D, E, T), dtype=torch.uint8, device=z.device)
+        # the 16-bit image of z (no indicator in it: each use names the halves'), kept for the backward's weight gradient
+        zt = torch.empty(lib.tt_latent16_image_bytes(B, CT, D, T), dtype=torch.uint8, device=z.device)
+        check(lib.tt_latent16_expand_reps(ptr(z), Dz, ctx.ind[0], ctx.ind[1], R, ptr(w), ptr(b), ptr(y), ptr(zt), ptr(ws), B, CT, D, E, T,
+                                          stream_ptr()), 'tt_latent16_expand_reps')
         ctx.params = (w, b)
-        ctx.save_for_backward(z, w, y)
+        ctx.zshape = (B, Dz, T)
+        ctx.save_for_backward(zt, w, y)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        z, w, y = ctx.saved_tensors
-        B, Dz, T = z.shape
+        zt, w, y = ctx.saved_tensors
+        B, Dz, T = ctx.zshape
         D, CT, E = w.size(0), w.size(1), w.size(2)
+        R = ctx.reps
         lib, st = lib16(y), stream_ptr()
         g = _as_cl16(dy, y.dtype)
-        ws = torch.empty(lib.tt_latent16_scratch_bytes(B, CT, D, E, T), dtype=torch.uint8, device=z.device)
+        ws = torch.empty(lib.tt_latent16_scratch_bytes(R * B, CT, D, E, T), dtype=torch.uint8, device=y.device)
         dz = rw = rb = None
         pre = ctx.link is not None and ctx.link.gated           # the transposed layer behind left dy * ELU'(y)
+        gy = None if pre else ptr(y)
         if ctx.needs_input_grad[0]:
-            dz = torch.empty_like(z)
-            if pre:
-                check(lib.tt_latent16_contract_pregated(ptr(g), ptr(w), ptr(dz), ptr(ws), B, CT, D, Dz, E, T, st), 'tt_latent16_contract_pregated')
-            else:
-                check(lib.tt_latent16_contract(ptr(g), ptr(y), ptr(w), None, ptr(dz), ptr(ws), B, CT, D, Dz, E, T, st), 'tt_latent16_contract')
+            dz = torch.empty((B, Dz, T), dtype=torch.float32, device=y.device)
+            check(lib.tt_latent16_contract_reps(ptr(g), gy, ptr(w), ptr(dz), ptr(ws), B, CT, D, Dz, E, T, R, st), 'tt_latent16_contract_reps')
         if ctx.needs_input_grad[1]:
             dw, rw = _grad_target(ctx.params[0])
             db, rb = _grad_target(ctx.params[1])
-            if pre:
-                check(lib.tt_latent16_wgrad_pregated(ptr(z), Dz, ctx.fill, ptr(g), ptr(dw), ptr(db), ptr(ws), B, CT, D, E, T, st),
-                      'tt_latent16_wgrad_pregated')
-            else:
-                check(lib.tt_latent16_wgrad(ptr(z), Dz, ctx.fill, ptr(g), ptr(y), ptr(dw), ptr(db), ptr(ws), B, CT, D, E, T, st), 'tt_latent16_wgrad')
-        return dz, rw, rb, None, None
+            check(lib.tt_latent16_wgrad_reps(ptr(zt), Dz, ctx.ind[0], ctx.ind[1], R, ptr(g), gy, ptr(dw), ptr(db), ptr(ws), B, CT, D, E, T, st),
+                  'tt_latent16_wgrad_reps')
+        return dz, rw, rb, None, None, None
