@@ -780,6 +780,53 @@ int tt_events_finish(const float* x, int B, int F, int T, double threshold, int 
                      const uint64_t* mask, const int* item, const int* row, const int* onset, const int* end, int64_t n_notes,
                      int min_frames, int* n_active, float* peak, int* keep, void* stream);
 
+/* ---- note-level scoring (csrc/notescore.hip; version 23) -----------------------------------------------------------------------------
+ * Precision / recall counts of estimated notes against reference notes, in the manner of mir_eval.transcription.match_notes, from notes
+ * that are on the device.  No reference counterpart: the reference has no note-level score.  The rule is the one stated in
+ * timbre_trap/utils/metrics.py (note_counts), evaluated in float64 with its expressions, so the counts are equal to the host's, not close
+ * to them: with rnd(x) = rint(x * 1e4) / 1e4, reference i and estimate k of one item are an ONSET PAIR when
+ * rnd(|on_i - on_k|) <= onset_tolerance && |p_i - p_k| <= pitch_tolerance, and also an OFFSET PAIR when
+ * rnd(|off_i - off_k|) <= max(offset_ratio * (off_i - on_i), offset_min_tolerance) (a NaN anywhere: not a pair).
+ * Both note lists are flat arrays sorted by (item, onset) -- NaN onsets last within an item -- with ref_seg / est_seg (n_items + 1 int64)
+ * the bounds of every item's run; items lie in [0, n_items) (a note outside has no partner).  Node v < n_ref is reference v, node
+ * n_ref + k is estimate k; n_ref, n_est >= 1 and n_ref + n_est < 2^31.  Nothing here uses atomics or recursion; every index read from an
+ * operand is clamped before it becomes an address; the results do not depend on the launch geometry.  A missing pointer or a size out
+ * of range: TT_E_BADARG and nothing is launched.
+ *   tt_notescore_max     references and estimates per connected component that tt_notescore_match holds (>= 64)
+ *   tt_notescore_times   onset[i] = (double)(onset_frame[i] * hop_int) * hop_mul / denom, offset[i] likewise from end_frame[i]: the
+ *                        arithmetic of events_to_notes (hop_int = hop_length, hop_mul = 1, denom = sample_rate; or hop_int = 1,
+ *                        hop_mul = seconds per frame, denom = 1), 1 <= n < 2^31
+ *   tt_notescore_ranges  lo[v], hi[v] (n_ref + n_est int32): the slice of the OTHER list, inside v's item, whose onsets lie within
+ *                        onset_tolerance + 1e-4 of v's -- a superset of v's onset pairs
+ *   tt_notescore_labels  one round of minimum-label propagation with pointer jumping over the onset pairs: label_out[v] = the smallest of
+ *                        label_in over v, its onset pairs and what following label_in from there reaches in six steps.  label_in !=
+ *                        label_out, n_ref + n_est int32 each, starting from label[v] = v.  Where label_out[v] != label_in[v]: *changed = 1
+ *                        and item_mark[item of v] = mark.  At the fixed point (a round that leaves *changed alone) label[v] is the smallest
+ *                        node of v's connected component
+ *   tt_notescore_match   label: the fixed point; {ref,est}_label_sorted / {ref,est}_perm: each side's labels in ascending order and the
+ *                        note index behind every position.  For reference v with label[v] == v: tp[v] / tp_no_offset[v] = size of a
+ *                        maximum matching of the offset-and-onset pairs / of the onset pairs within v's component; 0 for every other
+ *                        v < n_ref.  A component with more than tt_notescore_max references or estimates: both 0 and
+ *                        item_flag[item of v] = 1 (item_flag: n_items int32, zeroed by the caller)
+ *   tt_notescore_sums    out[b][5] int64 = {n_ref, n_est, sum tp, sum tp_no_offset, item_flag[b] != 0} of item b from its two runs */
+int tt_notescore_max(void);
+int tt_notescore_times(const int* onset_frame, const int* end_frame, int64_t n, int64_t hop_int, double hop_mul, double denom, double* onset,
+                       double* offset, void* stream);
+int tt_notescore_ranges(const int* ref_item, const double* ref_onset, int64_t n_ref, const int* est_item, const double* est_onset,
+                        int64_t n_est, const int64_t* ref_seg, const int64_t* est_seg, int n_items, double onset_tolerance, int* lo, int* hi,
+                        void* stream);
+int tt_notescore_labels(const int* ref_item, const double* ref_pitch, const double* ref_onset, int64_t n_ref, const int* est_item,
+                        const double* est_pitch, const double* est_onset, int64_t n_est, const int* lo, const int* hi,
+                        double onset_tolerance, double pitch_tolerance, const int* label_in, int* label_out, int* changed, int* item_mark,
+                        int n_items, int mark, void* stream);
+int tt_notescore_match(const int* label, const int* ref_label_sorted, const int* ref_perm, const int* est_label_sorted, const int* est_perm,
+                       const int* ref_item, const double* ref_pitch, const double* ref_onset, const double* ref_offset, int64_t n_ref,
+                       const double* est_pitch, const double* est_onset, const double* est_offset, int64_t n_est, double onset_tolerance,
+                       double pitch_tolerance, double offset_ratio, double offset_min_tolerance, int* tp, int* tp_no_offset, int* item_flag,
+                       int n_items, void* stream);
+int tt_notescore_sums(const int* tp, const int* tp_no_offset, int64_t n_ref, int64_t n_est, const int64_t* ref_seg, const int64_t* est_seg,
+                      const int* item_flag, int n_items, int64_t* out, void* stream);
+
 /* ---- frame-level pitch annotations to batched targets (csrc/pitch.hip; version 14) ---------------------------------------------------
  * Replaces, per item of an MPEDataset, PitchDataset.resample_multi_pitch (timbre_trap/datasets/PitchDataset.py:194-231: interp1d over the
  * track's frame times, then a list comprehension over the item's frames) followed by PitchDataset.multi_pitch_to_activations

@@ -42,7 +42,10 @@ SOURCES = ['cqt.hip', 'cqt_generic.hip', 'conv_generic.hip', 'conv_mfma.hip', 'c
            # (StemMixingDataset.__getitem__)
            'mix.hip',
            # note events (pitch row, onset, end, strength) from activation maps: bit-word run detection with gap filling
-           'events.hip']
+           'events.hip',
+           # note-level scores (estimated against reference notes): onset windows by binary search, connected components by label
+           # propagation, one maximum matching per component
+           'notescore.hip']
 
 _lib = None
 
@@ -211,6 +214,13 @@ _PROTOS = {
     'tt_events_count': (c_int, [P, I, I, I, I, P, P, P]),
     'tt_events_fill': (c_int, [P, I, I, I, I, P, P, L, P, P, P, P, P]),
     'tt_events_finish': (c_int, [P, I, I, I, ctypes.c_double, I, I, P, I, P, P, P, P, P, L, I, P, P, P, P]),
+    'tt_notescore_max': (c_int, []),
+    'tt_notescore_times': (c_int, [P, P, L, L, ctypes.c_double, ctypes.c_double, P, P, P]),
+    'tt_notescore_ranges': (c_int, [P, P, L, P, P, L, P, P, I, ctypes.c_double, P, P, P]),
+    'tt_notescore_labels': (c_int, [P, P, P, L, P, P, P, L, P, P, ctypes.c_double, ctypes.c_double, P, P, P, P, I, I, P]),
+    'tt_notescore_match': (c_int, [P, P, P, P, P, P, P, P, P, L, P, P, P, L, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                   ctypes.c_double, P, P, P, I, P]),
+    'tt_notescore_sums': (c_int, [P, P, L, L, P, P, P, I, P, P]),
     'tt_pitch_tile_frames': (c_int, []),
     'tt_pitch_max_bins': (c_int, []),
     'tt_pitch_max_radius': (c_int, []),

@@ -23,7 +23,8 @@ from .slicing import slice_audio, slice_times, resample_multi_pitch, nearest_ind
 from .metrics import (MultipitchEvaluator, multipitch_metrics, multipitch_metrics_device, multipitch_counts_device,
                       multipitch_metrics_device_notes, multipitch_counts_device_notes,
                       multipitch_metrics_device_track, multipitch_counts_device_track,
-                      signal_distortion_ratio, signal_distortion_ratio_device, SignalDistortionRatio)
+                      signal_distortion_ratio, signal_distortion_ratio_device, SignalDistortionRatio,
+                      note_counts, note_metrics, note_counts_device, note_metrics_device, NoteCounts, DeviceNoteCounts)
 from .notes import notes_to_multi_pitch, notes_csr_device, notes_to_activations, note_tiles
 from .events import NoteEvents, note_events, events_to_notes, write_midi
 from .pitch import PitchBank, pitch_to_activations, pitch_tiles
