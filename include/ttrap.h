@@ -780,6 +780,41 @@ int tt_events_finish(const float* x, int B, int F, int T, double threshold, int 
                      const uint64_t* mask, const int* item, const int* row, const int* onset, const int* end, int64_t n_notes,
                      int min_frames, int* n_active, float* peak, int* keep, void* stream);
 
+/* ---- pitch contours and pitch bends of note events (csrc/contours.hip; version 24) ----------------------------------------------------
+ * What the block above leaves behind: every pitch there is a bin centre or a row's number, while the map is sampled at several bins per
+ * semitone so that intonation, vibrato and slides show in it.  Here every frame of a note, or every entry of a per-frame bin list, gets
+ * a pitch refined below the bin spacing.  No reference counterpart: the reference stops at per-frame lists of bin centres.  Every result
+ * is an integer, an exact fp32 value, or a float64 value formed by a fixed sequence of individually rounded operations (nothing is
+ * contracted into a fused multiply-add; the divide is the correctly rounded one), so a restatement in NumPy scalars gives equal results.
+ * x, threshold, mode, f_valid, group_off, P: exactly as for tt_events_mask; the predicate is the same one.  m: the F float64 MIDI
+ * numbers of the bins (midi_freqs), on the device.
+ *   refine(f, t)      b = x[f], a = x[f - 1], c = x[f + 1] at frame t; a neighbour beyond either end or at f >= f_valid reads as 0.f.
+ *                     If a, b, c are all finite and b >= a and b >= c, in fp32: num = a - c; den = (a - b) + (c - b);
+ *                     delta = den < 0 ? 0.5f * (num / den) : 0.f (a NaN quotient, inf / inf: 0.f), clamped to [-0.5f, 0.5f].  Otherwise
+ *                     (a NaN or infinite sample, a plateau, in mode 1 a larger neighbour) delta = 0.f.  In float64:
+ *                     pitch = m[f] + (double)delta * step, step = m[f + 1] - m[f] for delta >= 0 and m[f] - m[f - 1] otherwise; where
+ *                     that neighbour does not exist, the other side's spacing; 0 at F = 1
+ *   tt_contours_notes   note i < n_notes is (item, row, onset, end)[i] as tt_events_fill wrote them, in any order; its end - onset frames
+ *                     own the slots [frame_off[i], frame_off[i + 1]) (frame_off: n_notes + 1 int64, the exclusive prefix sum of
+ *                     end - onset, formed by the caller).  Per frame t: among the bins of the row that pass the predicate the one with
+ *                     the largest x (ties: the lowest bin; +inf allowed) gives bin, value = x[bin], delta, pitch = refine(bin, t) and
+ *                     bend = (int32) rint((pitch - row_pitch[row]) * units) in float64, ties to even, clamped to [-2^30, 2^30], 0 for a
+ *                     non-finite product; a frame where no bin passes (bridged by max_gap) gives bin = -1, delta = 0, value = 0,
+ *                     pitch = NaN, bend = 0.  row_pitch: P float64 (the pitch of every row); units >= 1 bend units per semitone.
+ *                     Per note, over the frames with bin >= 0: n_voiced, bend_sum (int64), bend_min, bend_max (both 0 where n_voiced is
+ *                     0).  Every index read from item / row / onset / end / frame_off is clamped before it addresses memory; slots
+ *                     of a note beyond its clamped frames get the values of a frame where no bin passes
+ *   tt_contours_frames  x (F, T); est_off (T + 1 int64) / est_bins: the per-frame lists tt_mpe_fill wrote.  delta[j], pitch[j] =
+ *                     refine(est_bins[j], t) for est_off[t] <= j < est_off[t + 1]; nothing is written at or beyond `capacity`
+ * Nothing here uses atomics or reads the environment; every offset is 64-bit; the grids are one-dimensional; the results do not depend on
+ * the launch geometry.  Sizes >= 1 (capacity >= 0), mode 1 or 2, no null pointer: else TT_E_BADARG and nothing is launched. */
+int tt_contours_notes(const float* x, int B, int F, int T, double threshold, int mode, int f_valid, const int* group_off, int P,
+                      const double* m, const double* row_pitch, int units, const int* item, const int* row, const int* onset, const int* end,
+                      int64_t n_notes, const int64_t* frame_off, int* bin, float* delta, float* value, double* pitch, int* bend,
+                      int* n_voiced, int64_t* bend_sum, int* bend_min, int* bend_max, void* stream);
+int tt_contours_frames(const float* x, int F, int T, int f_valid, const int64_t* est_off, const int* est_bins, int64_t capacity,
+                       const double* m, float* delta, double* pitch, void* stream);
+
 /* ---- note-level scoring (csrc/notescore.hip; version 23) -----------------------------------------------------------------------------
  * Precision / recall counts of estimated notes against reference notes, in the manner of mir_eval.transcription.match_notes, from notes
  * that are on the device.  No reference counterpart: the reference has no note-level score.  The rule is the one stated in

@@ -45,7 +45,9 @@ SOURCES = ['cqt.hip', 'cqt_generic.hip', 'conv_generic.hip', 'conv_mfma.hip', 'c
            'events.hip',
            # note-level scores (estimated against reference notes): onset windows by binary search, connected components by label
            # propagation, one maximum matching per component
-           'notescore.hip']
+           'notescore.hip',
+           # per-frame pitch contours and pitch bends of note events, sub-bin pitches of per-frame bin lists: parabolic refinement
+           'contours.hip']
 
 _lib = None
 
@@ -214,6 +216,8 @@ _PROTOS = {
     'tt_events_count': (c_int, [P, I, I, I, I, P, P, P]),
     'tt_events_fill': (c_int, [P, I, I, I, I, P, P, L, P, P, P, P, P]),
     'tt_events_finish': (c_int, [P, I, I, I, ctypes.c_double, I, I, P, I, P, P, P, P, P, L, I, P, P, P, P]),
+    'tt_contours_notes': (c_int, [P, I, I, I, ctypes.c_double, I, I, P, I, P, P, I, P, P, P, P, L, P, P, P, P, P, P, P, P, P, P, P]),
+    'tt_contours_frames': (c_int, [P, I, I, I, P, P, L, P, P, P, P]),
     'tt_notescore_max': (c_int, []),
     'tt_notescore_times': (c_int, [P, P, L, L, ctypes.c_double, ctypes.c_double, P, P, P]),
     'tt_notescore_ranges': (c_int, [P, P, L, P, P, L, P, P, I, ctypes.c_double, P, P, P]),

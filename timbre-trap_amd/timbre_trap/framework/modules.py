@@ -389,6 +389,17 @@ class TimbreTrap(nn.Module):
         from ..utils.events import note_events
         return note_events(self.transcribe(audio), self.sliCQ.midi_freqs, **kwargs)
 
+    def transcribe_contours(self, audio, units_per_semitone=4096, **kwargs):
+        """audio (B,1,N) -> ``(NoteEvents, NoteContours)``: the notes of ``transcribe_notes(audio, **kwargs)`` and, from the same one run of
+        ``transcribe``, the per-frame pitch contour and pitch bends of every note (utils.contours.note_contours, formed on the device with
+        the grouping and threshold arguments of ``kwargs``)."""
+        from ..utils.contours import note_contours
+        from ..utils.events import note_events
+        activations, midi_freqs = self.transcribe(audio), self.sliCQ.midi_freqs
+        events = note_events(activations, midi_freqs, **kwargs)
+        shared = {k: kwargs[k] for k in ('t', 'peaks_only', 'n_valid_bins', 'resolution', 'bin_groups') if k in kwargs}
+        return events, note_contours(activations, events, midi_freqs, units_per_semitone=units_per_semitone, **shared)
+
     def reconstruct(self, audio_in):
         """audio (B,1,N) -> re-synthesised audio (B,1,L)."""
         return self.sliCQ.decode(self.chunked_inference(audio_in, False))

@@ -27,6 +27,8 @@ from .metrics import (MultipitchEvaluator, multipitch_metrics, multipitch_metric
                       note_counts, note_metrics, note_counts_device, note_metrics_device, NoteCounts, DeviceNoteCounts)
 from .notes import notes_to_multi_pitch, notes_csr_device, notes_to_activations, note_tiles
 from .events import NoteEvents, note_events, events_to_notes, write_midi
+from .contours import (NoteContours, note_contours, refined_pitches, refine_multi_pitch, activations_to_multi_pitch_refined,
+                       contours_to_bends, write_midi_bends)
 from .pitch import PitchBank, pitch_to_activations, pitch_tiles
 from .mixing import AudioBank, StemSource, StemMixer, mix_tiles, mix_targets
 from .audio import sinc_resample_kernel, resample_host, resample, mix_resample, prepare_audio
