@@ -818,7 +818,7 @@ int tt_contours_frames(const float* x, int F, int T, int f_valid, const int64_t*
 /* ---- note-level scoring (csrc/notescore.hip; version 23) -----------------------------------------------------------------------------
  * Precision / recall counts of estimated notes against reference notes, in the manner of mir_eval.transcription.match_notes, from notes
  * that are on the device.  No reference counterpart: the reference has no note-level score.  The rule is the one stated in
- * timbre_trap/utils/metrics.py (note_counts), evaluated in float64 with its expressions, so the counts are equal to the host's, not close
+ * timbre_trap/utils/metrics/notescore.py (note_counts), evaluated in float64 with its expressions, so the counts equal the host's, not close
  * to them: with rnd(x) = rint(x * 1e4) / 1e4, reference i and estimate k of one item are an ONSET PAIR when
  * rnd(|on_i - on_k|) <= onset_tolerance && |p_i - p_k| <= pitch_tolerance, and also an OFFSET PAIR when
  * rnd(|off_i - off_k|) <= max(offset_ratio * (off_i - on_i), offset_min_tolerance) (a NaN anywhere: not a pair).

@@ -126,7 +126,7 @@ def test_clique_at_and_over_the_capacity():
 def test_labels_that_do_not_settle_go_to_the_host(monkeypatch):
     """The chain of 60 needs five rounds; allowed two, its item is counted by the host function; the item beside it, whose components
     are pairs, has settled by then and is not."""
-    monkeypatch.setattr(metrics, 'NOTESCORE_ROUNDS', 2)
+    monkeypatch.setattr(metrics.notescore, 'NOTESCORE_ROUNDS', 2)             # the module whose global _note_counts_device reads
     score([chain(60), crafted()['pitch_boundary'][0]], n_fallback=1)
 
 

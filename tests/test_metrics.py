@@ -1,5 +1,5 @@
 """
-f2 row: the scoring restatements (timbre_trap/utils/metrics.py).  mir_eval and torchmetrics are absent from the image, so the
+f2 row: the scoring restatements (timbre_trap/utils/metrics/: multipitch.py, sdr.py).  mir_eval and torchmetrics are absent from the image, so the
 checks are known-answer tests worked by hand from the published definitions, an independent brute-force matcher, and -- for
 the SDR -- an independent dense least-squares derivation of the same quantity (projection onto 512 delayed copies).
 """

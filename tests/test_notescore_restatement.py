@@ -1,5 +1,5 @@
 """
-CPU-only: the note-level score of timbre_trap.utils.metrics (note_counts / note_metrics -- a restatement of
+CPU-only: the note-level score of timbre_trap.utils.metrics.notescore (note_counts / note_metrics -- a restatement of
 mir_eval.transcription's matching, unpinned against the package) against an independent route: the rule written a second time as
 dense hit matrices (tests/notescore_ref.py: dense_hits) and scipy's maximum bipartite matching; known answers; the boundaries of the
 three tolerances; and the component sizes of the generated cases, which keep tests/test_gpu_notescore.py honest about its fallback.

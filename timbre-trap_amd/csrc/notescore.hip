@@ -1,5 +1,5 @@
 // Note-level scoring on the device (include/ttrap.h: tt_notescore_*): integers and float64 comparisons only, no atomics, no recursion,
-// every loop with a static bound.  The rule is stated once, in utils/metrics.py (note_counts); ns_onset_pair / ns_offset_pair below are
+// every loop with a static bound.  The rule is stated once, in utils/metrics/notescore.py (note_counts); ns_onset_pair / ns_offset_pair below are
 // its two predicates, expression for expression.
 //
 //   notes sorted by (item, onset) on both sides (the caller sorts); node v < R is reference v, node R + k is estimate k

@@ -22,6 +22,7 @@ import torch
 
 from .. import _hip
 from .events import _event_activations, _pitch_rows, _vlq
+from .metrics.mpe import _mpe_activations, mpe_compact
 
 __all__ = ['NoteContours', 'note_contours', 'refined_pitches', 'refine_multi_pitch', 'activations_to_multi_pitch_refined',
            'contours_to_bends', 'write_midi_bends']
@@ -110,7 +111,6 @@ def refine_multi_pitch(activations, midi_freqs, t=0.5, peaks_only=True, n_valid_
     int32 [n], delta float32 [n], pitch float64 [n])``, frame f's entries at ``est_off[f]:est_off[f + 1]``.  ``delta`` and ``pitch``
     as in ``note_contours``.  ``activations``: a CUDA tensor (F, T) or (1, F, T).
     """
-    from .metrics import _mpe_activations, mpe_compact
     x = _mpe_activations(activations)
     F, T = x.shape
     midi_freqs = np.array(midi_freqs, dtype=np.float64)

@@ -6,7 +6,7 @@ such a dataset (``experiments/evaluate.py:76-78,116``).
 
 ``PitchBank`` keeps the annotations of a whole dataset on the device, uploaded once: per value the nearest bin and the scorer's MIDI
 number, per source frame the row offsets and the 'lost' byte, per track the frame times -- all formed on the host, vectorised over every
-value, with the very expressions of the list-based code (``utils/targets.py``, ``utils/metrics.py``), so equality with that code holds
+value, with the very expressions of the list-based code (``utils/targets.py``, ``utils/metrics/multipitch.py``), so equality with that code holds
 by construction.  What scales with the items runs in HIP kernels (csrc/pitch.hip):
 
   tt_pitch_nearest   (item, frame) -> the source frame it reads, ``nearest_indices``' float64 comparisons by binary search
@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from .. import _hip
+from .metrics.multipitch import MAX_FREQ, MIN_FREQ, frequencies_to_midi
 from .notes import _cuda_device, _is_sorted, _note_bins
 from .slicing import resample_multi_pitch
 from .targets import _gaussian_weights, multi_pitch_to_activations
@@ -45,7 +46,6 @@ def _bank_arrays(tracks, midi_freqs, resample_idcs):
       or out-of-range pitch), lost uint8 [R], midi float64 [V] (the scorer's numbers), outside bool [n] (``_mpe_reference_csr``'s range
       check per track), device_ok bool [n] (times non-decreasing and finite).
     """
-    from .metrics import MAX_FREQ, MIN_FREQ, frequencies_to_midi
     times, frames, table = [], [], np.zeros((len(tracks), 4), dtype=np.int64)
     device_ok = np.zeros(len(tracks), dtype=bool)
     base = 0

@@ -61,7 +61,7 @@ def main():
     ap.add_argument('--frames', type=int, default=102400)
     args = ap.parse_args()
     from timbre_trap.utils import activations_to_multi_pitch, multipitch_metrics, multipitch_metrics_device, to_array
-    from timbre_trap.utils.metrics import mpe_compact, multipitch_counts_device
+    from timbre_trap.utils.metrics.mpe import mpe_compact, multipitch_counts_device
     dev = torch.device('cuda:0')
     midi_freqs = 16.76557586 + np.arange(F) / 5.0
     x = synthetic_track(args.frames, dev)

@@ -65,7 +65,7 @@ def main():
     ap.add_argument('--seconds', type=float, default=300.0)
     args = ap.parse_args()
     from timbre_trap.utils import note_counts, note_counts_device
-    from timbre_trap.utils.metrics import _kuhn
+    from timbre_trap.utils.metrics.notescore import _kuhn
     if not torch.cuda.is_available():
         raise SystemExit('kb_notescore.py measures on the GPU; there is none here')
     dev = torch.device('cuda:0')
