@@ -815,6 +815,45 @@ int tt_contours_notes(const float* x, int B, int F, int T, double threshold, int
 int tt_contours_frames(const float* x, int F, int T, int f_valid, const int64_t* est_off, const int* est_bins, int64_t capacity,
                        const double* m, float* delta, double* pitch, void* stream);
 
+/* ---- exact t-SNE in two dimensions (csrc/tsne.hip; version 25) ------------------------------------------------------------------------
+ * Replaces the TSNE(n_components=2, perplexity=5, n_iter=1000).fit_transform of plot_latents (timbre_trap/utils/visualization.py:139-144)
+ * as experiments/latents.py:111-131 calls it on the time-averaged latents of the Bach10 stems -- a call the installed scikit-learn (>= 1.7,
+ * which removed n_iter) refuses -- for codes that are already on the device, and for the thousands of per-frame codes the host route does
+ * not reach.  The algorithm is scikit-learn's method='exact': float64 throughout, two output dimensions, no atomics, no environment
+ * switches; every sum runs in an order that depends on N alone, so two runs agree bit for bit and a run split in two equals the whole.
+ * 2 <= N <= 16384 (P within 2 GiB), D >= 1, 0 < perplexity < N, no null pointer, every pointer a multiple of 8 bytes: else TT_E_BADARG and
+ * nothing is launched.  All pointers are device pointers; the entries neither allocate nor synchronise.
+ *   tt_tsne_scratch_bytes  (visualization.py:139-144; latents.py:111-131) bytes of `scratch` for the other two entries; TT_E_BADARG for an N
+ *                          out of range
+ *   tt_tsne_affinities     (visualization.py:139-144; latents.py:111-131) x (N, D), fp32 (dtype 0) or fp64 (dtype 1), converted to float64.
+ *                          d_ij = sum over d ascending of (x_id - x_jd)^2, every operation rounded on its own (not the Gram identity): d_ij
+ *                          and d_ji are the same bits and d_ii = 0.  Per row i scikit-learn's search for beta_i such that the entropy of
+ *                          p_j ~ exp(-beta_i d_ij), j != i, equals log(perplexity): beta = 1; per evaluation s = sum_j exp(-beta d_ij)
+ *                          (1e-8 where that is 0), H = log(s) + beta (sum_j d_ij exp(-beta d_ij)) / s; H > log(perplexity): the lower bound
+ *                          becomes beta, and beta doubles (no upper bound yet) or moves to the midpoint; otherwise the mirror image with
+ *                          halving.  EXACTLY 128 evaluations, no tolerance exit: a bracket closes to rounding, and beta stays finite
+ *                          (2^+-127) where it never brackets.  beta_i (output, N doubles) and s_i are those of the last evaluation.
+ *                          C_ij = exp(-beta_i d_ij) / s_i, P_ij = max((C_ij + C_ji) / T, DBL_EPSILON) for i != j and 0 on the diagonal,
+ *                          T = max(sum_ij (C_ij + C_ji), DBL_EPSILON) added in a fixed order.  P (output, N x N doubles) is symmetric bit
+ *                          for bit; the distances exist only in its buffer
+ *   tt_tsne_run            (visualization.py:139-144; latents.py:111-131) iterations it0 .. it1 - 1 (0 <= it0 <= it1) of scikit-learn's
+ *                          _gradient_descent on the caller's state Y, U (the update), gains, each N x 2 doubles, in and out; one call
+ *                          enqueues all its iterations.  At iteration it: e = exaggeration and m = momentum0 while it < explore_iters, else
+ *                          e = 1 and m = momentum1.  w_ij = 1 / (1 + |y_i - y_j|^2), Z = sum_{i != j} w_ij,
+ *                          grad_i = 4 (e sum_j p_ij w_ij (y_i - y_j) - (sum_j w_ij^2 (y_i - y_j)) / Z) -- scikit-learn's
+ *                          4 sum_j (e p_ij - q_ij) w_ij (y_i - y_j) without its clamp of q_ij = w_ij / Z at DBL_EPSILON, which needs
+ *                          |y_i - y_j| > 1e7 / N to act; gains += 0.2 where U grad < 0, else gains *= 0.8, floored at min_gain;
+ *                          U = m U - learning_rate (grad gains); Y += U.  There is NO early stop (it would take a host round trip per
+ *                          check): exactly it1 - it0 iterations run.  Afterwards, from the FINAL Y and without exaggeration:
+ *                          kl_out[0] = sum_{i != j} p_ij log(max(p_ij, eps) / max(w_ij / Z, eps)), eps = DBL_EPSILON, and gnorm_out[0] = the
+ *                          2-norm of grad (e = 1); it0 == it1 computes only these.  exaggeration, learning_rate > 0, momenta in [0, 1),
+ *                          min_gain >= 0, explore_iters >= 0 */
+int64_t tt_tsne_scratch_bytes(int N);
+int tt_tsne_affinities(const void* x, int dtype, int N, int D, double perplexity, double* P, double* beta, void* scratch, void* stream);
+int tt_tsne_run(const double* P, int N, double* Y, double* U, double* gains, int it0, int it1, int explore_iters, double exaggeration,
+                double learning_rate, double momentum0, double momentum1, double min_gain, double* kl_out, double* gnorm_out, void* scratch,
+                void* stream);
+
 /* ---- note-level scoring (csrc/notescore.hip; version 23) -----------------------------------------------------------------------------
  * Precision / recall counts of estimated notes against reference notes, in the manner of mir_eval.transcription.match_notes, from notes
  * that are on the device.  No reference counterpart: the reference has no note-level score.  The rule is the one stated in

@@ -709,7 +709,7 @@ extern "C" int tt_set_cu_limit(int cus) {
     return prev;
 }
 
-extern "C" int tt_version(void) { return 24; }   // 24: pitch contours and pitch bends of note events (csrc/contours.hip: tt_contours_*)   // 23: note-level scores (csrc/notescore.hip: tt_notescore_*)   // 22: the pair forms of the decoder latent head (csrc/latent_bf16.hip: tt_latent16_*_reps, tt_latent16_image_bytes)   // 21: note events from activation maps (csrc/events.hip: tt_events_*)   // 20: phase retrieval for the magnitude models (tt_cqt_griffin_lim)   // 18: random stem mixtures of a training batch (csrc/mix.hip: tt_mix_*)   // 17: the FiLM layer of TimbreTrapFiLM (csrc/film.hip: tt_film_fwd / tt_film_bwd)   // 16: the positive return code "level done, join not" and the A/B kernel routes behind it removed (tt_wide_level_bwd_gated_join returns 0 or an error; tt_wide_scratch_bytes without the dA1 region at C = 4, 8, 16; k_wrb_dxw at C = 32 only)   // 15: registers and private memory of the block-backward kernels (tt_wide_bwd_kernel_attr)   // 14: frame-level pitch annotations to batched targets (csrc/pitch.hip: tt_pitch_*)   // 13: note annotations to per-frame lists and targets (csrc/notes.hip: tt_note_*; tt_target_activations_spans)   // 12: mono mix, sample-rate conversion and inf-norm of tracks (csrc/resample.hip: tt_resample*)   // 11: multi-pitch scoring on the device (csrc/mpe.hip: tt_mpe_*)   // 10: the device-side signal-distortion ratio (csrc/sdr.hip: tt_sdr_*)   // 9: split-operand training of the wide blocks (tt_x3_rb_fwd_train, tt_x3_rb_bwd, tt_x3_grad_scale, tt_x3_{pack,unpack}_scaled)   // 8: the magnitude variants (tt_cqt_forward_mag, tt_magnitude, tt_decibels, tt_act_bwd, TT_ACT_RELU / TT_ACT_SIGMOID, tt_activations1_*)   // 7: tt_channel_sum_ws (the channel sum in a fixed order)   // 6: tt_skip_join16_{fwd,bwd} (the skip joins of the 16-bit path in one pass each way)   // 5: gate links (tt_wide_level_bwd_gated, tt_*_bwd_pregated, tt_latent16_*_{gated,pregated}, tt_gate16)   // 4: any-block-length CQT, tt_set_loss_scale, tt_adamw_step(skipped)   // 3: bf16 channels-last entry points (tt_wide_*, tt_sconv16_*, tt_tconv16_*, tt_latent16_*, tt_conv{in,out}16_*)
+extern "C" int tt_version(void) { return 25; }   // 24: pitch contours and pitch bends of note events (csrc/contours.hip: tt_contours_*)   // 23: note-level scores (csrc/notescore.hip: tt_notescore_*)   // 22: the pair forms of the decoder latent head (csrc/latent_bf16.hip: tt_latent16_*_reps, tt_latent16_image_bytes)   // 21: note events from activation maps (csrc/events.hip: tt_events_*)   // 20: phase retrieval for the magnitude models (tt_cqt_griffin_lim)   // 18: random stem mixtures of a training batch (csrc/mix.hip: tt_mix_*)   // 17: the FiLM layer of TimbreTrapFiLM (csrc/film.hip: tt_film_fwd / tt_film_bwd)   // 16: the positive return code "level done, join not" and the A/B kernel routes behind it removed (tt_wide_level_bwd_gated_join returns 0 or an error; tt_wide_scratch_bytes without the dA1 region at C = 4, 8, 16; k_wrb_dxw at C = 32 only)   // 15: registers and private memory of the block-backward kernels (tt_wide_bwd_kernel_attr)   // 14: frame-level pitch annotations to batched targets (csrc/pitch.hip: tt_pitch_*)   // 13: note annotations to per-frame lists and targets (csrc/notes.hip: tt_note_*; tt_target_activations_spans)   // 12: mono mix, sample-rate conversion and inf-norm of tracks (csrc/resample.hip: tt_resample*)   // 11: multi-pitch scoring on the device (csrc/mpe.hip: tt_mpe_*)   // 10: the device-side signal-distortion ratio (csrc/sdr.hip: tt_sdr_*)   // 9: split-operand training of the wide blocks (tt_x3_rb_fwd_train, tt_x3_rb_bwd, tt_x3_grad_scale, tt_x3_{pack,unpack}_scaled)   // 8: the magnitude variants (tt_cqt_forward_mag, tt_magnitude, tt_decibels, tt_act_bwd, TT_ACT_RELU / TT_ACT_SIGMOID, tt_activations1_*)   // 7: tt_channel_sum_ws (the channel sum in a fixed order)   // 6: tt_skip_join16_{fwd,bwd} (the skip joins of the 16-bit path in one pass each way)   // 5: gate links (tt_wide_level_bwd_gated, tt_*_bwd_pregated, tt_latent16_*_{gated,pregated}, tt_gate16)   // 4: any-block-length CQT, tt_set_loss_scale, tt_adamw_step(skipped)   // 3: bf16 channels-last entry points (tt_wide_*, tt_sconv16_*, tt_tconv16_*, tt_latent16_*, tt_conv{in,out}16_*)
 extern "C" const char* tt_arch(void) { return "gfx950"; }
 extern "C" const char* tt_error_string(int code) {
     if (code == 0) return "ok";

@@ -47,7 +47,9 @@ SOURCES = ['cqt.hip', 'cqt_generic.hip', 'conv_generic.hip', 'conv_mfma.hip', 'c
            # propagation, one maximum matching per component
            'notescore.hip',
            # per-frame pitch contours and pitch bends of note events, sub-bin pitches of per-frame bin lists: parabolic refinement
-           'contours.hip']
+           'contours.hip',
+           # exact t-SNE of latent codes in two dimensions, float64 with fixed-order sums: joint probabilities and gradient descent
+           'tsne.hip']
 
 _lib = None
 
@@ -218,6 +220,10 @@ _PROTOS = {
     'tt_events_finish': (c_int, [P, I, I, I, ctypes.c_double, I, I, P, I, P, P, P, P, P, L, I, P, P, P, P]),
     'tt_contours_notes': (c_int, [P, I, I, I, ctypes.c_double, I, I, P, I, P, P, I, P, P, P, P, L, P, P, P, P, P, P, P, P, P, P, P]),
     'tt_contours_frames': (c_int, [P, I, I, I, P, P, L, P, P, P, P]),
+    'tt_tsne_scratch_bytes': (c_int64, [I]),
+    'tt_tsne_affinities': (c_int, [P, I, I, I, ctypes.c_double, P, P, P, P]),
+    'tt_tsne_run': (c_int, [P, I, P, P, P, I, I, I, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                            P, P, P, P]),
     'tt_notescore_max': (c_int, []),
     'tt_notescore_times': (c_int, [P, P, L, L, ctypes.c_double, ctypes.c_double, P, P, P]),
     'tt_notescore_ranges': (c_int, [P, P, L, P, P, L, P, P, I, ctypes.c_double, P, P, P]),

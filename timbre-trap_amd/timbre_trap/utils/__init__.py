@@ -29,6 +29,7 @@ from .notes import notes_to_multi_pitch, notes_csr_device, notes_to_activations,
 from .events import NoteEvents, note_events, events_to_notes, write_midi
 from .contours import (NoteContours, note_contours, refined_pitches, refine_multi_pitch, activations_to_multi_pitch_refined,
                        contours_to_bends, write_midi_bends)
+from .embedding import TSNEResult, TSNEState, tsne_joint_probabilities, tsne, latent_codes, plot_latents_device
 from .pitch import PitchBank, pitch_to_activations, pitch_tiles
 from .mixing import AudioBank, StemSource, StemMixer, mix_tiles, mix_targets
 from .audio import sinc_resample_kernel, resample_host, resample, mix_resample, prepare_audio
